@@ -11,6 +11,9 @@ Contract (driver):
   python bench.py --gpus N --steps K --warmup W
   (N>1 is launched via torch.distributed.run, one rank per GPU over RCCL;
   rank 0 prints ONE JSON line.)
+A plain run sets up, warms up, times the K steps and prints the line;
+--dump-outputs DIR also writes the last timed step's outputs as .npy, and
+--full is where any secondary measurement or check belongs.
 
 Secondary configs (BASELINE.json configs[2..5]) via --algo:
   --algo PPO | V-MPO | SAC | PPO-Continuous | SAC-Continuous
@@ -70,6 +73,42 @@ def make_synthetic_batch(params, device, seed):
     return {k: v.to(device) for k, v in batch.items()}
 
 
+DUMP_BUDGET_BYTES = 64 * 1024 * 1024  # --dump-outputs writes at most this
+
+
+def step_outputs(updater, stats):
+    """What a caller of the timed path holds after a step: the step's stat
+    scalars plus the weights it has just updated (every trainable module and
+    loose parameter of the updater), as name → fp32 numpy array."""
+    out = {}
+    for k, v in (stats or {}).items():
+        out[f"stat_{k}"] = torch.as_tensor(v).detach().float().cpu().reshape(1).numpy()
+    for mod_name, mod in updater.trainable_modules().items():
+        for k, v in mod.state_dict().items():
+            out[f"param_{mod_name}.{k}"] = v.detach().float().cpu().numpy()
+    for k, v in updater.extra_params().items():
+        out[f"param_{k}"] = v.detach().float().cpu().numpy()
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array as <out_dir>/<name>.npy (float32). An array over its
+    share of the byte budget is replaced by a fixed, seeded sample of its
+    flattened elements, so two builds dump the same positions."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    per_array = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        keep = per_array // a.itemsize
+        if a.size > keep:
+            idx = np.random.default_rng(0).choice(a.size, size=keep, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(out_dir / f"{name.replace('/', '_')}.npy", a)
+
+
 def _self_exec_torchrun(n: int):
     """--gpus N launched as a plain `python bench.py`: re-exec under
     torch.distributed.run so N ranks actually do the work. Without this,
@@ -107,6 +146,16 @@ def main():
     ap.add_argument("--algo", default="IMPALA",
                     choices=["IMPALA", "PPO", "V-MPO", "SAC",
                              "PPO-Continuous", "SAC-Continuous"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned and updated (stat scalars, weights) "
+                         "as DIR/<name>.npy, float32; inputs are seeded, so "
+                         "two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks. "
+                         "A plain run does only what the headline figure "
+                         "needs; at present the benchmark has no secondary "
+                         "work, so this adds nothing yet")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -167,7 +216,7 @@ def main():
 
         def step_fn():
             dev_batch = stager.stage(host_np)   # fill overlaps prev GPU tail
-            updater.step(dev_batch)
+            stats = updater.step(dev_batch)
             if wpub is not None:
                 if state["pending"]:
                     header, payload = encode(Protocol.Model, wpub.finish(),
@@ -175,11 +224,12 @@ def main():
                     pub.send(header, payload)   # overlaps THIS step on GPU
                 wpub.begin()                    # D2H queued after the step
                 state["pending"] = True
+            return stats
     else:
         batch = make_synthetic_batch(params, device, seed=100 + rank)
 
         def step_fn():
-            updater.step(batch)
+            return updater.step(batch)
 
     import torch.distributed as dist
 
@@ -197,9 +247,10 @@ def main():
     barrier()
     sync()
 
+    last_stats = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step_fn()
+        last_stats = step_fn()
     sync()
     barrier()
     sync()
@@ -215,6 +266,8 @@ def main():
     transitions = n_gpus * args.batch_size * args.seq_len * args.steps
     value = transitions / elapsed
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, step_outputs(updater, last_stats))
         result = {
             "metric": "learner_env_steps_per_sec",
             "value": value,
