@@ -267,8 +267,12 @@ def learner_sub_process(learner_ip, learner_port, *_):
     # manager routes rollouts across shards by worker connection.
     from pdrl_amd.agents import storage_shard_ports
 
+    # device actor mode: the learner rank(s) roll out on the GPU themselves —
+    # no storage process (and no manager / worker roles) to feed them
+    device_actor = getattr(params, "actor_mode", "workers") == "device"
     n_shards = max(1, int(getattr(params, "storage_shards", 1) or 1))
-    for k, port in enumerate(storage_shard_ports(learner_port, n_shards)):
+    shard_ports = [] if device_actor else storage_shard_ports(learner_port, n_shards)
+    for k, port in enumerate(shard_ports):
         hb_storage = mp.Value("d", time.time())
         sup.spawn(f"storage-{k}", storage_run,
                   (ring, learner_ip, port, params,

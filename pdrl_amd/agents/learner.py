@@ -14,7 +14,11 @@ MI355X-first differences:
   batch from the ring and all-reduces gradients over RCCL/xGMI via
   GradReducer (reference has a single-GPU learner only);
 * batch staging goes through a pinned-host buffer + async H2D copy
-  (BatchStager below) instead of per-field blocking copies.
+  (BatchStager below) instead of per-field blocking copies;
+* device actor mode (``"actor_mode": "device"``): for native envs with
+  discrete policies the learner rolls out on the GPU itself
+  (ops/rollout.py) and needs no ring, storage, manager or workers — see
+  ``Learner._init_device_actor``. Env state is not checkpointed.
 """
 from __future__ import annotations
 
@@ -260,6 +264,10 @@ class Learner:
         self.updater = maybe_graph(self.updater, self.device)
 
         self.on_policy = is_on_policy(params.algo)
+        self.device_rollout = None
+        if getattr(params, "actor_mode", "workers") == "device":
+            self._init_device_actor()
+            return
         self.stager = BatchStager(self.device)
         self._rng = np.random.default_rng(1234 + rank)
         self.is_root = rank == 0
@@ -292,6 +300,52 @@ class Learner:
         self.timer = ExecutionTimer(num_transition=params.seq_len * params.batch_size * world_size)
         self._replay_ready = False  # latching (reference: learner.py:385)
 
+    def _init_device_actor(self):
+        """Device actor mode (``actor_mode == "device"``): the rollout never
+        leaves the GPU. A ``DeviceRollout`` on the updater's actor core steps
+        ``device_envs`` (0 = ``batch_size``) native envs per update and hands
+        the learner its batch in place — no workers, manager, storage
+        process, H2D staging or weight broadcast (the PUB socket is not
+        bound), and the data is exactly on-policy: ``log_prob`` / ``logits``
+        come from the weights the update is about to use. On-policy algos
+        train on the rollout itself; discrete SAC appends it to the
+        ``DeviceReplay`` and samples. The ring is never read or written.
+        Env state is not checkpointed: a resumed run starts fresh episodes.
+        """
+        from pdrl_amd.ops.rollout import DeviceRollout, has_device_env
+
+        p = self.params
+        if p.algo.endswith("Continuous") or getattr(p, "continuous", False):
+            raise ValueError(
+                f"actor_mode='device' supports discrete policies only "
+                f"(algo {p.algo!r} is continuous); use actor_mode='workers'")
+        if not has_device_env(p.env):
+            raise ValueError(
+                f"actor_mode='device': env {p.env!r} has no device dynamics; "
+                f"use actor_mode='workers'")
+        mods = self.updater.trainable_modules()
+        m = mods.get("model") or next(iter(mods.values()))
+        actor = getattr(m, "actor", m)
+        n_envs = int(getattr(p, "device_envs", 0) or 0) or p.batch_size
+        self.device_rollout = DeviceRollout(
+            actor.core, p.env, n_envs, p.seq_len, self.device,
+            seed=1234 + self.rank, time_horizon=p.time_horizon)
+        self.is_root = self.rank == 0
+        self.device_replay = None
+        if not self.on_policy:
+            from pdrl_amd.buffers.device_replay import DeviceReplay
+
+            self.device_replay = DeviceReplay(
+                self.device_rollout.fields, p.seq_len, p.buffer_size,
+                self.device, seed=1234 + self.rank)
+        self.pub = None
+        self.weight_pub = None
+        self.weight_pub_async = None
+        self.writer = SummaryWriter(p.result_dir) if self.is_root else None
+        self.timer = ExecutionTimer(
+            num_transition=p.seq_len * p.batch_size * self.world_size)
+        self._replay_ready = False
+
     # ------------------------------------------------------------------ #
     def _stopped(self) -> bool:
         return self.stop_event is not None and self.stop_event.is_set()
@@ -313,6 +367,16 @@ class Learner:
 
     def next_batch(self, timeout: float = 30.0):
         """Block until a batch is available (or timeout/stop). Stages to device."""
+        if self.device_rollout is not None:
+            if self._stopped():
+                return None
+            batch = self.device_rollout.rollout()
+            if self.device_replay is None:
+                return batch
+            self.device_replay.append_batch(batch)
+            while self.device_replay.size < self.params.batch_size:  # warm-up
+                self.device_replay.append_batch(self.device_rollout.rollout())
+            return self.device_replay.sample(self.params.batch_size)
         deadline = time.monotonic() + timeout
         b = self.params.batch_size
         while not self._stopped() and time.monotonic() < deadline:
@@ -362,6 +426,14 @@ class Learner:
             for name, dq in self.timer.timer_dict.items():
                 if dq:
                     self.writer.add_scalar(f"{name}-sec", float(np.mean(dq)), n)
+            if self.device_rollout is not None:
+                games, mean50 = self.device_rollout.episode_stats()
+                if self.shared_stat is not None:
+                    self.shared_stat[0], self.shared_stat[1] = games, mean50
+                if games > 0:
+                    self.writer.add_scalar("game-count", games, n)
+                    self.writer.add_scalar("50-game-mean-stat-of-epi-rew", mean50, n)
+                return
             if self.shared_stat is not None and self.shared_stat[2] >= 1.0:
                 self.writer.add_scalar("game-count", self.shared_stat[0], n)
                 self.writer.add_scalar("50-game-mean-stat-of-epi-rew", self.shared_stat[1], n)

@@ -47,6 +47,14 @@ bool megastep_onpolicy_hip(
     double, double, double, double, double, double, double, double, double,
     double, double, double, double, double, double, bool, long);
 void barrier_bench_hip(at::Tensor&, long, long);
+void rollout_discrete_hip(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, at::Tensor&,
+    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, long,
+    long, long, long);
+double rollout_uniform_host(long, long, long, long);
 void seq_lstm_fwd_loss_hip(
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
@@ -273,6 +281,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("megastep_onpolicy", &megastep_onpolicy_hip,
         "ENTIRE IMPALA/PPO training step in one launch (fwd+loss+bwd+wgrad"
         "+RMSprop between grid barriers); false => shape not co-resident");
+  m.def("rollout_discrete", &rollout_discrete_hip,
+        "device actor: N envs x S steps of policy-act + env-step in one "
+        "launch, writing the learner's (N,S,.) batch fields in place",
+        py::arg("body_w"), py::arg("body_b"), py::arg("w_ih"), py::arg("w_hh"),
+        py::arg("b_g"), py::arg("heads_w"), py::arg("heads_b"),
+        py::arg("env_state"), py::arg("h"), py::arg("c"), py::arg("is_fir"),
+        py::arg("ep_steps"), py::arg("ep_run"), py::arg("tick"),
+        py::arg("obs"), py::arg("act"), py::arg("rew"), py::arg("logits"),
+        py::arg("log_prob"), py::arg("is_fir_out"), py::arg("hx"),
+        py::arg("cx"), py::arg("ep_ret"), py::arg("env_id"), py::arg("seed"),
+        py::arg("time_horizon"), py::arg("max_episode_steps"));
+  m.def("rollout_uniform", &rollout_uniform_host,
+        "host evaluation of the rollout's counter-hash uniform",
+        py::arg("seed"), py::arg("env"), py::arg("tick"), py::arg("k"));
   m.def("barrier_bench", &barrier_bench_hip,
         "grid-barrier microbenchmark (N back-to-back barriers)");
   m.def("seq_lstm_fwd_loss", &seq_lstm_fwd_loss_hip,

@@ -1,0 +1,501 @@
+// Device actor: fused policy-act + env-step rollout for CDNA4 (gfx950).
+//
+// One launch advances N native environments by S steps and writes the
+// (N, S, ·) batch in the learner's own field layout (buffers.rollout_fields)
+// straight into persistent device tensors: policy forward, categorical
+// sample, log-prob, env dynamics, termination and auto-reset never leave the
+// GPU. The single-call CPU counterpart is cpu_actor.cpp::act_batch_discrete;
+// the eager oracle is pdrl_amd/ops/rollout.py.
+//
+// Geometry: as seq_lstm_fwd_row (core_rows.h) — one 4H-thread workgroup per
+// environment, thread = gate column with its w_ih / w_hh column resident in
+// 2×H VGPRs, loaded once per launch and amortised over the S steps. The
+// environments are independent, so there is no inter-workgroup traffic and
+// no atomics: episode returns are written per (env, step) and reduced
+// lazily by the host. obs, xb, h, c, gates and the logits head columns live
+// in LDS (a few KB). The logits are a wave-0 butterfly reduction; thread 0
+// then samples while wave 1 steps the dynamics for every action (lane =
+// action) and draws the reset uniforms, so the two scalar chains overlap.
+// Five barriers a step.
+//
+// Random numbers come from the stateless counter hash in rollout_rng.h,
+// keyed by (seed, env, tick, lane): per-env tick counters live on device and
+// are advanced by the kernel, so replays and re-launches never repeat draws.
+
+#include "common.h"
+#include "rollout_rng.h"
+
+#include <algorithm>
+#include <cstdint>
+
+namespace {
+
+// "No episode ended at this step" marker in ep_ret (any real return is far
+// above it, negative-reward envs included).
+constexpr float kNoEpisode = -1.0e30f;
+
+// ---- native env dynamics -------------------------------------------------
+// An env is a traits struct: kObsDim, kActions, reset(state, u[4]) and
+// step(state, action, reward, terminated). A second env is one more struct
+// and one more case in rollout_discrete_hip.
+
+// CartPole-v1: constants and Euler update of pdrl_amd/envs/cartpole.py, fp32.
+struct CartPoleDyn {
+  static constexpr int kObsDim = 4;
+  static constexpr int kActions = 2;
+
+  __device__ static void reset(float* s, const float* u) {
+    // explicit mul-then-add (no fma contraction): bit-exact vs the oracle
+#pragma unroll
+    for (int i = 0; i < kObsDim; ++i)
+      s[i] = __fadd_rn(-0.05f, __fmul_rn(0.1f, u[i]));
+  }
+
+  __device__ static void step(float* s, int a, float& reward,
+                              bool& terminated) {
+    constexpr float kGravity = 9.8f, kMassPole = 0.1f, kTotalMass = 1.1f;
+    constexpr float kLength = 0.5f, kPoleMassLength = 0.05f;
+    constexpr float kForceMag = 10.0f, kTau = 0.02f;
+    constexpr float kThetaThreshold = 0.20943951023931953f;  // 12 degrees
+    constexpr float kXThreshold = 2.4f;
+    float x = s[0], x_dot = s[1], theta = s[2], theta_dot = s[3];
+    const float force = (a == 1) ? kForceMag : -kForceMag;
+    const float cos_t = cosf(theta), sin_t = sinf(theta);
+    const float temp =
+        (force + kPoleMassLength * theta_dot * theta_dot * sin_t) / kTotalMass;
+    const float theta_acc =
+        (kGravity * sin_t - cos_t * temp) /
+        (kLength * (4.0f / 3.0f - kMassPole * cos_t * cos_t / kTotalMass));
+    const float x_acc = temp - kPoleMassLength * theta_acc * cos_t / kTotalMass;
+    x = x + kTau * x_dot;
+    x_dot = x_dot + kTau * x_acc;
+    theta = theta + kTau * theta_dot;
+    theta_dot = theta_dot + kTau * theta_acc;
+    s[0] = x; s[1] = x_dot; s[2] = theta; s[3] = theta_dot;
+    terminated = x < -kXThreshold || x > kXThreshold ||
+                 theta < -kThetaThreshold || theta > kThetaThreshold;
+    reward = 1.0f;
+  }
+};
+
+struct RolloutArgs {
+  // live policy weights (transposed layout, read by pointer every launch)
+  const float* body_w;   // (F, H)
+  const float* body_b;   // (H)
+  const float* w_ih;     // (H, 4H)
+  const float* w_hh;     // (H, 4H)
+  const float* b_g;      // (4H)
+  const float* heads_w;  // (H, D) — columns [0, A) are the logits head
+  const float* heads_b;  // (D)
+  // persistent per-env state (read and written)
+  float* env_state;      // (N, F)
+  float* h;              // (N, H)
+  float* c;              // (N, H)
+  float* is_fir;         // (N)
+  int* ep_steps;         // (N)
+  float* ep_run;         // (N) running episode return
+  unsigned* tick;        // (N) steps taken since construction
+  // outputs, (N, S, ·)
+  float* obs;
+  float* act;
+  float* rew;
+  float* logits;
+  float* log_prob;
+  float* is_fir_out;
+  float* hx;
+  float* cx;
+  float* ep_ret;         // (N, S)
+  int N, S, D;
+  unsigned seed;
+  int time_horizon, max_episode_steps;
+};
+
+template <int H, typename Env>
+__global__ __launch_bounds__(4 * H) void rollout_discrete(RolloutArgs p) {
+  constexpr int G = 4 * H;
+  constexpr int F = Env::kObsDim;
+  constexpr int A = Env::kActions;
+  const int tid = threadIdx.x;
+  const int n = blockIdx.x;
+  if (n >= p.N) return;  // uniform per workgroup
+
+  __shared__ __attribute__((aligned(16))) float s_xb[H];
+  __shared__ __attribute__((aligned(16))) float s_h[H];
+  __shared__ __attribute__((aligned(16))) float s_c[H];
+  __shared__ __attribute__((aligned(16))) float s_gates[G];
+  __shared__ float s_hw[A * H];  // logits head columns, [a][k]
+  __shared__ float s_obs[F];
+  __shared__ float s_cand[A * F];  // next state for every action
+  __shared__ float s_crew[A];
+  __shared__ int s_cterm[A];
+  __shared__ float s_ur[4];  // reset uniforms of this tick
+  __shared__ float s_fir;
+  __shared__ int s_reset;
+
+  // Register-resident gate weight columns (thread = gate column tid). A
+  // 4H-thread workgroup has a 256-VGPR budget per thread, which holds both
+  // columns (2H values) only up to H = 64; at H = 128 the w_hh column stays
+  // in registers and the w_ih column is streamed per step (coalesced,
+  // L2-resident, S·H loads per thread) — no scratch in either case.
+  constexpr bool kWihRegs = H <= 64;
+  constexpr int HW = kWihRegs ? H : 4;
+  float wih[HW], whh[H];
+  if constexpr (kWihRegs) {
+#pragma unroll
+    for (int k = 0; k < H; ++k) wih[k] = p.w_ih[k * G + tid];
+    PDRL_PIN_REGS(wih, H);
+  }
+#pragma unroll
+  for (int k = 0; k < H; ++k) whh[k] = p.w_hh[k * G + tid];
+  PDRL_PIN_REGS(whh, H);
+  const float bias = p.b_g[tid];
+  float hb[A];
+#pragma unroll
+  for (int a = 0; a < A; ++a) hb[a] = p.heads_b[a];
+
+  // body column of thread j < H (F is a handful of values)
+  float bw[F];
+  float bb = 0.0f;
+  if (tid < H) {
+#pragma unroll
+    for (int k = 0; k < F; ++k) bw[k] = p.body_w[k * H + tid];
+    bb = p.body_b[tid];
+    s_h[tid] = p.h[(long)n * H + tid];
+    s_c[tid] = p.c[(long)n * H + tid];
+  } else {
+#pragma unroll
+    for (int k = 0; k < F; ++k) bw[k] = 0.0f;
+  }
+  for (int idx = tid; idx < A * H; idx += G) {
+    const int a = idx / H, k = idx % H;
+    s_hw[idx] = p.heads_w[k * p.D + a];
+  }
+  if (tid < F) s_obs[tid] = p.env_state[(long)n * F + tid];
+
+  // episode bookkeeping lives in thread 0's registers across the S steps
+  int steps = 0;
+  float run = 0.0f;
+  unsigned tick = p.tick[n];  // every thread tracks it (hash counter)
+  if (tid == 0) {
+    s_fir = p.is_fir[n];
+    steps = p.ep_steps[n];
+    run = p.ep_run[n];
+  }
+  __syncthreads();
+
+  for (int t = 0; t < p.S; ++t) {
+    const long row = (long)n * p.S + t;
+    tick += 1u;
+    // record the pre-step obs / hx / cx / is_fir; body GEMV + ReLU
+    if (tid < F) p.obs[row * F + tid] = s_obs[tid];
+    if (tid == 0) p.is_fir_out[row] = s_fir;
+    if (tid < H) {
+      p.hx[row * H + tid] = s_h[tid];
+      p.cx[row * H + tid] = s_c[tid];
+      float acc = bb;
+#pragma unroll
+      for (int k = 0; k < F; ++k) acc = fmaf(s_obs[k], bw[k], acc);
+      s_xb[tid] = fmaxf(acc, 0.0f);
+    }
+    __syncthreads();
+
+    // gates (b128 LDS broadcast reads against register weight columns)
+    {
+      const float4* xb4 = reinterpret_cast<const float4*>(s_xb);
+      const float4* h4 = reinterpret_cast<const float4*>(s_h);
+      float acc = bias;
+      // streamed mode: re-derive the column pointer opaquely every step, or
+      // the loop-invariant loads get hoisted out of the t loop into (spilt)
+      // registers — the same compiler habit PDRL_PIN_REGS counters
+      const float* wcol = p.w_ih + tid;
+      if constexpr (!kWihRegs) asm volatile("" : "+v"(wcol));
+#pragma unroll
+      for (int k = 0; k < H / 4; ++k) {
+        const float4 xv = xb4[k];
+        if constexpr (!kWihRegs) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) wih[j] = wcol[(4 * k + j) * G];
+        }
+        const int w = kWihRegs ? 4 * k : 0;
+        acc = fmaf(xv.x, wih[w], acc);
+        acc = fmaf(xv.y, wih[w + 1], acc);
+        acc = fmaf(xv.z, wih[w + 2], acc);
+        acc = fmaf(xv.w, wih[w + 3], acc);
+      }
+#pragma unroll
+      for (int k = 0; k < H / 4; ++k) {
+        const float4 hv = h4[k];
+        acc = fmaf(hv.x, whh[4 * k], acc);
+        acc = fmaf(hv.y, whh[4 * k + 1], acc);
+        acc = fmaf(hv.z, whh[4 * k + 2], acc);
+        acc = fmaf(hv.w, whh[4 * k + 3], acc);
+      }
+      const int sel = tid / H;  // 0:i 1:f 2:g 3:o
+      const float g = (sel == 2) ? tanhf(acc) : sigmoidf_dev(acc);
+      s_gates[tid] = g;
+    }
+    __syncthreads();
+
+    // cell update
+    if (tid < H) {
+      const float c_new =
+          s_gates[H + tid] * s_c[tid] + s_gates[tid] * s_gates[2 * H + tid];
+      s_c[tid] = c_new;
+      s_h[tid] = s_gates[3 * H + tid] * tanhf(c_new);
+    }
+    __syncthreads();
+
+    // logits = head columns [0, A): wave 0 splits the H-long dot products
+    // over its lanes and butterfly-reduces them (a serial loop in one lane
+    // is ~H dependent LDS round trips — it dominated the step)
+    float lg[A];
+    if (tid < kWave) {
+#pragma unroll
+      for (int a = 0; a < A; ++a) {
+        float part = 0.0f;
+        for (int k = tid; k < H; k += kWave)
+          part = fmaf(s_h[k], s_hw[a * H + k], part);
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1)
+          part += __shfl_xor(part, off, kWave);
+        lg[a] = part + hb[a];
+      }
+    } else if (tid < kWave + A) {
+      // meanwhile wave 1 steps the dynamics for EVERY action (lane = action)
+      // and draws the reset uniforms: the two single-lane scalar chains
+      // (softmax/sample/log-prob vs sin/cos/divides) run side by side
+      const int a = tid - kWave;
+      float st[F];
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+      float reward;
+      bool terminated;
+      Env::step(st, a, reward, terminated);
+#pragma unroll
+      for (int k = 0; k < F; ++k) s_cand[a * F + k] = st[k];
+      s_crew[a] = reward;
+      s_cterm[a] = terminated ? 1 : 0;
+    } else if (tid < kWave + A + 4) {
+      const unsigned k = (unsigned)(tid - kWave - A);
+      s_ur[k] = pdrl_rng::uniform(p.seed, (unsigned)n, tick, k + 1u);
+    }
+
+    // softmax, sample, log-prob (thread 0, no barrier needed: it already
+    // holds the reduced logits)
+    int chosen = A - 1;
+    if (tid == 0) {
+      float mx = lg[0];
+#pragma unroll
+      for (int a = 0; a < A; ++a) {
+        p.logits[row * A + a] = lg[a];
+        mx = fmaxf(mx, lg[a]);
+      }
+      float prob[A];
+      float Z = 0.0f;
+#pragma unroll
+      for (int a = 0; a < A; ++a) {
+        prob[a] = expf(lg[a] - mx);
+        Z += prob[a];
+      }
+      // inverse CDF against one uniform (rule of cpu_actor.cpp)
+      const float u = pdrl_rng::uniform(p.seed, (unsigned)n, tick, 0u);
+      float cdf = 0.0f;
+      bool found = false;
+      float lg_chosen = lg[A - 1];
+#pragma unroll
+      for (int a = 0; a < A; ++a) {  // static indices: lg/prob stay in VGPRs
+        cdf += prob[a] / Z;
+        if (!found && u < cdf) {
+          chosen = a;
+          lg_chosen = lg[a];
+          found = true;
+        }
+      }
+      p.act[row] = (float)chosen;
+      p.log_prob[row] = lg_chosen - mx - logf(Z);
+    }
+    __syncthreads();
+
+    // pick the sampled action's outcome; termination, auto-reset (thread 0)
+    if (tid == 0) {
+      float st[F];
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = s_cand[chosen * F + k];
+      const float reward = s_crew[chosen];
+      const bool terminated = s_cterm[chosen] != 0;
+      steps += 1;
+      run += reward;
+      p.rew[row] = reward;
+      const bool done = terminated || steps >= p.max_episode_steps;
+      const bool reset = done || steps >= p.time_horizon;
+      p.ep_ret[row] = reset ? run : kNoEpisode;
+      if (reset) {
+        Env::reset(st, s_ur);
+        steps = 0;
+        run = 0.0f;
+      }
+#pragma unroll
+      for (int k = 0; k < F; ++k) s_obs[k] = st[k];
+      s_fir = reset ? 1.0f : 0.0f;
+      s_reset = reset ? 1 : 0;
+    }
+    __syncthreads();
+    // thread j is the only reader of s_h[j] / s_c[j] before the next barrier
+    if (s_reset != 0 && tid < H) {
+      s_h[tid] = 0.0f;
+      s_c[tid] = 0.0f;
+    }
+  }
+
+  // persist the per-env state for the next launch
+  if (tid < H) {
+    p.h[(long)n * H + tid] = s_h[tid];
+    p.c[(long)n * H + tid] = s_c[tid];
+  }
+  if (tid < F) p.env_state[(long)n * F + tid] = s_obs[tid];
+  if (tid == 0) {
+    p.is_fir[n] = s_fir;
+    p.ep_steps[n] = steps;
+    p.ep_run[n] = run;
+    p.tick[n] = tick;
+  }
+}
+
+template <typename Env>
+void launch_env(const RolloutArgs& a, int H) {
+  const dim3 grid(a.N);
+  switch (H) {
+    case 32:
+      hipLaunchKernelGGL((rollout_discrete<32, Env>), grid, dim3(128), 0,
+                         current_stream(), a);
+      break;
+    case 64:
+      hipLaunchKernelGGL((rollout_discrete<64, Env>), grid, dim3(256), 0,
+                         current_stream(), a);
+      break;
+    case 128:
+      hipLaunchKernelGGL((rollout_discrete<128, Env>), grid, dim3(512), 0,
+                         current_stream(), a);
+      break;
+    default:
+      TORCH_CHECK(false, "hidden size ", H, " unsupported (32/64/128)");
+  }
+  HIP_CHECK_LAST();
+}
+
+void check_i32(const at::Tensor& t, long n, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == at::kInt && t.numel() == n,
+              name, " must be a contiguous int32 GPU tensor of ", n,
+              " elements");
+}
+
+void check_f32(const at::Tensor& t, long n, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&
+                  t.scalar_type() == at::kFloat && t.numel() == n,
+              name, " must be a contiguous float32 GPU tensor of ", n,
+              " elements");
+}
+
+}  // namespace
+
+// env_id: 0 = CartPole-v1 (ids are assigned in pdrl_amd/ops/rollout.py).
+void rollout_discrete_hip(
+    const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
+    const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
+    const at::Tensor& heads_b, at::Tensor& env_state, at::Tensor& h,
+    at::Tensor& c, at::Tensor& is_fir, at::Tensor& ep_steps,
+    at::Tensor& ep_run, at::Tensor& tick, at::Tensor& obs, at::Tensor& act,
+    at::Tensor& rew, at::Tensor& logits, at::Tensor& log_prob,
+    at::Tensor& is_fir_out, at::Tensor& hx, at::Tensor& cx,
+    at::Tensor& ep_ret, long env_id, long seed, long time_horizon,
+    long max_episode_steps) {
+  CHECK_IN(body_w); CHECK_IN(body_b); CHECK_IN(w_ih); CHECK_IN(w_hh);
+  CHECK_IN(b_g); CHECK_IN(heads_w); CHECK_IN(heads_b);
+  TORCH_CHECK(body_w.dim() == 2 && w_ih.dim() == 2 && heads_w.dim() == 2 &&
+                  env_state.dim() == 2 && obs.dim() == 3,
+              "rollout: bad tensor ranks");
+  const long F = body_w.size(0), H = body_w.size(1), D = heads_w.size(1);
+  const long N = env_state.size(0), S = obs.size(1);
+  int A = 0;
+  switch (env_id) {
+    case 0:
+      TORCH_CHECK(F == CartPoleDyn::kObsDim, "CartPole needs obs_dim 4");
+      A = CartPoleDyn::kActions;
+      break;
+    default:
+      TORCH_CHECK(false, "rollout: unknown device env id ", env_id);
+  }
+  TORCH_CHECK(N >= 1 && S >= 1, "rollout: empty batch");
+  TORCH_CHECK(D >= A && heads_w.size(0) == H, "heads_w shape");
+  check_f32(body_b, H, "body_b");
+  check_f32(w_ih, H * 4 * H, "w_ih");
+  check_f32(w_hh, H * 4 * H, "w_hh");
+  check_f32(b_g, 4 * H, "b_g");
+  check_f32(heads_b, D, "heads_b");
+  check_f32(env_state, N * F, "env_state");
+  check_f32(h, N * H, "h");
+  check_f32(c, N * H, "c");
+  check_f32(is_fir, N, "is_fir state");
+  check_i32(ep_steps, N, "ep_steps");
+  check_f32(ep_run, N, "ep_run");
+  check_i32(tick, N, "tick");
+  check_f32(obs, N * S * F, "obs");
+  check_f32(act, N * S, "act");
+  check_f32(rew, N * S, "rew");
+  check_f32(logits, N * S * A, "logits");
+  check_f32(log_prob, N * S, "log_prob");
+  check_f32(is_fir_out, N * S, "is_fir");
+  check_f32(hx, N * S * H, "hx");
+  check_f32(cx, N * S * H, "cx");
+  check_f32(ep_ret, N * S, "ep_ret");
+  const auto dev = body_w.device();
+  for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{
+        &body_b, &w_ih, &w_hh, &b_g, &heads_w, &heads_b, &env_state, &h, &c,
+        &is_fir, &ep_steps, &ep_run, &tick, &obs, &act, &rew, &logits,
+        &log_prob, &is_fir_out, &hx, &cx, &ep_ret})
+    TORCH_CHECK(t->device() == dev, "rollout: tensors on different devices");
+  TORCH_CHECK(time_horizon >= 1 && max_episode_steps >= 1,
+              "rollout: horizons must be positive");
+
+  RolloutArgs a;
+  a.body_w = body_w.data_ptr<float>();
+  a.body_b = body_b.data_ptr<float>();
+  a.w_ih = w_ih.data_ptr<float>();
+  a.w_hh = w_hh.data_ptr<float>();
+  a.b_g = b_g.data_ptr<float>();
+  a.heads_w = heads_w.data_ptr<float>();
+  a.heads_b = heads_b.data_ptr<float>();
+  a.env_state = env_state.data_ptr<float>();
+  a.h = h.data_ptr<float>();
+  a.c = c.data_ptr<float>();
+  a.is_fir = is_fir.data_ptr<float>();
+  a.ep_steps = ep_steps.data_ptr<int>();
+  a.ep_run = ep_run.data_ptr<float>();
+  a.tick = reinterpret_cast<unsigned*>(tick.data_ptr<int>());
+  a.obs = obs.data_ptr<float>();
+  a.act = act.data_ptr<float>();
+  a.rew = rew.data_ptr<float>();
+  a.logits = logits.data_ptr<float>();
+  a.log_prob = log_prob.data_ptr<float>();
+  a.is_fir_out = is_fir_out.data_ptr<float>();
+  a.hx = hx.data_ptr<float>();
+  a.cx = cx.data_ptr<float>();
+  a.ep_ret = ep_ret.data_ptr<float>();
+  a.N = (int)N;
+  a.S = (int)S;
+  a.D = (int)D;
+  a.seed = (unsigned)seed;
+  a.time_horizon = (int)std::min<long>(time_horizon, INT32_MAX);
+  a.max_episode_steps = (int)std::min<long>(max_episode_steps, INT32_MAX);
+
+  switch (env_id) {
+    case 0: launch_env<CartPoleDyn>(a, (int)H); break;
+  }
+}
+
+// Host evaluation of the rollout's uniform (same header as the kernel).
+double rollout_uniform_host(long seed, long env, long tick, long k) {
+  return (double)pdrl_rng::uniform((uint32_t)seed, (uint32_t)env,
+                                   (uint32_t)tick, (uint32_t)k);
+}

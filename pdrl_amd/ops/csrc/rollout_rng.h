@@ -1,0 +1,37 @@
+// Counter-based random stream of the device rollout (rollout.hip), shared
+// by the kernel and host code so a test can reproduce it bit for bit.
+// Stateless: a uniform is a pure function of (seed, env, tick, lane), which
+// is what makes the stream graph-safe and independent of launch geometry.
+// All arithmetic is uint32 (wrap-around); the torch mirror of this file is
+// pdrl_amd/ops/rollout.py::uniform.
+#pragma once
+
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#define PDRL_HD __host__ __device__ __forceinline__
+#else
+#define PDRL_HD inline
+#endif
+
+namespace pdrl_rng {
+
+PDRL_HD uint32_t wang(uint32_t s) {
+  s = (s ^ 61u) ^ (s >> 16);
+  s *= 9u;
+  s ^= s >> 4;
+  s *= 0x27d4eb2du;
+  s ^= s >> 15;
+  return s;
+}
+
+// Lane k of env's draw at ``tick``: k = 0 is the action uniform, k = 1..4
+// the reset state of a reset caused by the step at ``tick`` (tick 0: the
+// initial state at construction). Result in [0, 1), a multiple of 2^-24.
+PDRL_HD float uniform(uint32_t seed, uint32_t env, uint32_t tick, uint32_t k) {
+  const uint32_t h0 = wang(seed ^ (env * 0x9E3779B1u));
+  const uint32_t h = wang(h0 ^ wang(tick * 8u + k + 0x85ebca6bu));
+  return static_cast<float>(h >> 8) * (1.0f / 16777216.0f);
+}
+
+}  // namespace pdrl_rng

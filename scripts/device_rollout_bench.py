@@ -1,0 +1,103 @@
+"""Device actor mode throughput (env-steps/s), host clock closed by a
+synchronize, 50 warm-up calls, timed windows of at least ``--window`` s.
+
+    python scripts/device_rollout_bench.py [--repeats 3] [--window 1.0]
+
+(a) ``rollout()`` alone at N=128 and N=1024 (S=5, H=64);
+(b) rollout + IMPALA update in device mode at B=128 — the end-to-end figure
+    to hold against ``bench.py --mode staged`` (the path this mode replaces)
+    and ``--mode resident`` (the ceiling: no data path at all).
+
+Prints one JSON line per measurement; ``values`` holds every repeat.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO))
+
+import torch  # noqa: E402
+
+WARMUP = 50
+
+
+def timed(fn, window_s: float, steps_per_call: int, chunk: int) -> float:
+    """env-steps/s over one window of >= window_s (whole chunks of calls)."""
+    torch.cuda.synchronize()
+    calls = 0
+    t0 = time.perf_counter()
+    while True:
+        for _ in range(chunk):
+            fn()
+        calls += chunk
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        if el >= window_s:
+            return calls * steps_per_call / el
+
+
+def report(name: str, values: list[float], **cfg):
+    print(json.dumps({
+        "metric": name, "unit": "env-steps/s",
+        "median": sorted(values)[len(values) // 2],
+        "min": min(values), "max": max(values), "values": values, **cfg,
+    }), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--window", type=float, default=1.0)
+    ap.add_argument("--seq-len", type=int, default=5)
+    ap.add_argument("--hidden", type=int, default=64)
+    args = ap.parse_args()
+
+    assert torch.cuda.is_available(), "needs a GPU"
+    from pdrl_amd.agents.learner_module import ImpalaUpdater
+    from pdrl_amd.networks import MlpLSTMSingle
+    from pdrl_amd.ops.rollout import DeviceRollout
+    from pdrl_amd.utils import load_params
+
+    dev, S, H = "cuda:0", args.seq_len, args.hidden
+
+    # (a) rollout alone
+    for n_envs in (128, 1024):
+        torch.manual_seed(0)
+        model = MlpLSTMSingle(4, 2, S, H).to(dev)
+        ro = DeviceRollout(model.actor.core, "CartPole-v1", n_envs, S, dev,
+                           seed=1, time_horizon=500)
+        for _ in range(WARMUP):
+            ro.rollout()
+        vals = [timed(ro.rollout, args.window, n_envs * S, 200)
+                for _ in range(args.repeats)]
+        report("rollout_only", vals, num_envs=n_envs, seq_len=S, hidden=H)
+
+    # (b) rollout + IMPALA update, device mode, B=128
+    p = load_params()
+    p.algo, p.batch_size, p.seq_len, p.hidden_size = "IMPALA", 128, S, H
+    p.obs_dim, p.n_actions = 4, 2
+    torch.manual_seed(1234)
+    model = MlpLSTMSingle(4, 2, S, H)
+    upd = ImpalaUpdater(model, p, dev)
+    ro = DeviceRollout(upd.model.actor.core, "CartPole-v1", p.batch_size, S,
+                       dev, seed=1234, time_horizon=p.time_horizon)
+
+    def step():
+        upd.step(ro.rollout())
+
+    for _ in range(WARMUP):
+        step()
+    vals = [timed(step, args.window, p.batch_size * S, 200)
+            for _ in range(args.repeats)]
+    games, mean50 = ro.episode_stats()
+    report("device_mode_impala", vals, batch_size=p.batch_size, seq_len=S,
+           hidden=H, episodes=games, mean50=mean50)
+
+
+if __name__ == "__main__":
+    main()

@@ -69,6 +69,9 @@ def main():
     ap.add_argument("--entropy", type=float, default=None)
     ap.add_argument("--clip", type=float, default=None, help="max_grad_norm")
     ap.add_argument("--batch-size", type=int, default=None)
+    ap.add_argument("--actor", choices=("workers", "device"), default="workers",
+                    help="device: the learner rolls out on the GPU itself "
+                         "(no manager / worker processes)")
     ap.add_argument("--set", action="append", default=[],
                     help="extra param override key=value (repeatable)")
     args = ap.parse_args()
@@ -88,6 +91,7 @@ def main():
         base["max_grad_norm"] = args.clip
     if args.batch_size is not None:
         base["batch_size"] = args.batch_size
+    base["actor_mode"] = args.actor
     for kv in args.set:
         k, v = kv.split("=", 1)
         try:
@@ -120,8 +124,9 @@ def main():
 
     t0 = time.monotonic()
     spawn("learner_sub_process", "127.0.0.1", lrn_port)
-    spawn("manager_sub_process", "127.0.0.1", "127.0.0.1", mgr_port, lrn_port)
-    spawn("worker_sub_process", args.workers, "127.0.0.1", "127.0.0.1", mgr_port, lrn_port)
+    if args.actor == "workers":
+        spawn("manager_sub_process", "127.0.0.1", "127.0.0.1", mgr_port, lrn_port)
+        spawn("worker_sub_process", args.workers, "127.0.0.1", "127.0.0.1", mgr_port, lrn_port)
 
     deadline = t0 + args.minutes * 60
     result_dir = None
@@ -162,7 +167,8 @@ def main():
             except subprocess.TimeoutExpired:
                 pr.kill()
     out = {
-        "algo": args.algo, "env": args.env, "workers": args.workers,
+        "algo": args.algo, "env": args.env, "actor": args.actor,
+        "workers": args.workers if args.actor == "workers" else 0,
         "target": args.target, "time_to_target_s": reached,
         "best_50_game_mean": best if best > -1e9 else None,
         "elapsed_s": time.monotonic() - t0,

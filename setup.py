@@ -30,6 +30,7 @@ SRC = [
     "pdrl_amd/ops/csrc/multi_tensor.hip",
     "pdrl_amd/ops/csrc/megastep.hip",
     "pdrl_amd/ops/csrc/fwd_loss.hip",
+    "pdrl_amd/ops/csrc/rollout.hip",
 ]
 
 setup(
