@@ -97,11 +97,15 @@ class VMPOUpdater(BaseUpdater):
 
         value_loss = F.smooth_l1_loss(value[:, :-1], td_target)
 
+        # logit L2, as in the IMPALA/PPO losses and the fused V-MPO kernels
+        logit_reg = float(getattr(p, "logit_reg", 0.0))
+        reg_loss = logits[:, :-1].pow(2).mean() if logit_reg > 0 else 0.0
         loss = (
             p.policy_loss_coef * policy_loss
             + p.value_loss_coef * value_loss
             + eta_loss
             + alpha_loss
+            + logit_reg * reg_loss
         )
         stats = {
             "loss-total": loss.detach(),

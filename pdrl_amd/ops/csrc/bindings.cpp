@@ -34,19 +34,6 @@ void seq_lstm_backward_multi_hip(const at::Tensor&, const at::Tensor&,
 void seq_lstm_wgrad_multi_hip(const at::Tensor&, const at::Tensor&,
                               const at::Tensor&, long, long,
                               const c10::optional<at::Tensor>&, long, long);
-bool megastep_onpolicy_hip(
-    const at::Tensor&, const at::Tensor&, const at::Tensor&,
-    const at::Tensor&, const at::Tensor&, const at::Tensor&,
-    const at::Tensor&, const at::Tensor&, const at::Tensor&,
-    const at::Tensor&, const at::Tensor&, const at::Tensor&,
-    const at::Tensor&, const at::Tensor&, at::Tensor&, at::Tensor&,
-    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
-    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
-    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
-    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, long,
-    double, double, double, double, double, double, double, double, double,
-    double, double, double, double, double, double, bool, long);
-void barrier_bench_hip(at::Tensor&, long, long);
 void rollout_discrete_hip(
     const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
     const at::Tensor&, const at::Tensor&, const at::Tensor&, at::Tensor&,
@@ -75,6 +62,20 @@ void seq_lstm_bwd_fin_hip(
     const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&,
     const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&,
     const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&);
+void onpolicy_loss_rows_hip(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, at::Tensor&, at::Tensor&,
+    const c10::optional<at::Tensor>&, long, double, double, double, double,
+    double, double, double, double, double, double, double,
+    const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&,
+    const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&);
+void onpolicy_stats_fin_hip(const at::Tensor&, at::Tensor&, long, long, long,
+                            long, double, double, double, double);
+void vmpo_grad_rows_hip(const at::Tensor&, const at::Tensor&,
+                        const at::Tensor&, const at::Tensor&,
+                        const at::Tensor&, const at::Tensor&,
+                        const at::Tensor&, at::Tensor&, double, double,
+                        double);
 bool vmpo_mid_hip(const at::Tensor&, const at::Tensor&, const at::Tensor&,
                   const at::Tensor&, const at::Tensor&, const at::Tensor&,
                   const at::Tensor&, const at::Tensor&, at::Tensor&,
@@ -86,53 +87,6 @@ std::vector<at::Tensor> vtrace_hip(const at::Tensor&, const at::Tensor&,
                                    const at::Tensor&, const at::Tensor&,
                                    const at::Tensor&, double, double, double,
                                    double, long, long, double);
-std::vector<at::Tensor> cat_stats_hip(const at::Tensor&, const at::Tensor&,
-                                      long);
-std::vector<at::Tensor> ppo_td_gae_hip(const at::Tensor&, const at::Tensor&,
-                                       const at::Tensor&, long, double, double,
-                                       double);
-void impala_loss_reduce_hip(const at::Tensor&, const at::Tensor&,
-                            const at::Tensor&, long, const at::Tensor&,
-                            const at::Tensor&, const at::Tensor&, at::Tensor&,
-                            double, double, double, double);
-void ppo_loss_reduce_hip(const at::Tensor&, const at::Tensor&,
-                         const at::Tensor&, const at::Tensor&, long,
-                         const at::Tensor&, const at::Tensor&, at::Tensor&,
-                         double, double, double, double, double);
-at::Tensor impala_loss_bwd_hip(const at::Tensor&, long, const at::Tensor&,
-                               const at::Tensor&, const at::Tensor&,
-                               const at::Tensor&, const at::Tensor&, double,
-                               double, double, double);
-at::Tensor ppo_loss_bwd_hip(const at::Tensor&, long, const at::Tensor&,
-                            const at::Tensor&, const at::Tensor&,
-                            const at::Tensor&, const at::Tensor&,
-                            const at::Tensor&, const at::Tensor&, double,
-                            double, double, double, double);
-bool impala_loss_mega_hip(const at::Tensor&, const at::Tensor&,
-                          const at::Tensor&, const at::Tensor&,
-                          const at::Tensor&, at::Tensor&, at::Tensor&,
-                          const c10::optional<at::Tensor>&, long, double,
-                          double, double, double, double, double, double,
-                          double, double);
-bool ppo_loss_mega_hip(const at::Tensor&, const at::Tensor&, const at::Tensor&,
-                       const at::Tensor&, const at::Tensor&, at::Tensor&,
-                       at::Tensor&, const c10::optional<at::Tensor>&, long,
-                       double, double, double, double, double, double,
-                       double, double);
-bool vmpo_loss_mega_hip(const at::Tensor&, const at::Tensor&,
-                        const at::Tensor&, const at::Tensor&,
-                        const at::Tensor&, const at::Tensor&,
-                        const at::Tensor&, at::Tensor&, at::Tensor&,
-                        at::Tensor&, at::Tensor&,
-                        const c10::optional<at::Tensor>&, at::Tensor&, long,
-                        double, double, double, double, double, double,
-                        double, double, double, long);
-bool ppoc_loss_mega_hip(const at::Tensor&, const at::Tensor&,
-                        const at::Tensor&, const at::Tensor&,
-                        const at::Tensor&, at::Tensor&, at::Tensor&,
-                        const c10::optional<at::Tensor>&, long, double,
-                        double, double, double, double, double, double,
-                        double);
 void sac_actor_loss_hip(const at::Tensor&, const at::Tensor&,
                         const at::Tensor&, const at::Tensor&, at::Tensor&,
                         at::Tensor&, at::Tensor&,
@@ -278,9 +232,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("h0"), py::arg("tab"), py::arg("C"),
         py::arg("D"), py::arg("x2") = c10::nullopt, py::arg("F2") = 0,
         py::arg("half") = 0);
-  m.def("megastep_onpolicy", &megastep_onpolicy_hip,
-        "ENTIRE IMPALA/PPO training step in one launch (fwd+loss+bwd+wgrad"
-        "+RMSprop between grid barriers); false => shape not co-resident");
   m.def("rollout_discrete", &rollout_discrete_hip,
         "device actor: N envs x S steps of policy-act + env-step in one "
         "launch, writing the learner's (N,S,.) batch fields in place",
@@ -295,8 +246,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rollout_uniform", &rollout_uniform_host,
         "host evaluation of the rollout's counter-hash uniform",
         py::arg("seed"), py::arg("env"), py::arg("tick"), py::arg("k"));
-  m.def("barrier_bench", &barrier_bench_hip,
-        "grid-barrier microbenchmark (N back-to-back barriers)");
   m.def("seq_lstm_fwd_loss", &seq_lstm_fwd_loss_hip,
         "forward + row-local loss (IMPALA/PPO/PPO-C, V-MPO pre) in ONE "
         "launch",
@@ -324,6 +273,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vm_td") = c10::nullopt,
         py::arg("vm_scalars") = c10::nullopt,
         py::arg("vm_outs") = c10::nullopt);
+  m.def("onpolicy_loss_rows", &onpolicy_loss_rows_hip,
+        "row-local loss (IMPALA/PPO/PPO-C, V-MPO pre) over the outputs of "
+        "seq_lstm_forward, one block per batch row",
+        py::arg("outs"), py::arg("act"), py::arg("behav"), py::arg("rew"),
+        py::arg("fir"), py::arg("gouts"), py::arg("stats_part"),
+        py::arg("norm_sq"), py::arg("algo"), py::arg("gamma"),
+        py::arg("lmbda"), py::arg("rho_bar"), py::arg("rho_min"),
+        py::arg("c_bar"), py::arg("rew_scale"), py::arg("cp"), py::arg("cv"),
+        py::arg("ce"), py::arg("eps_clip"), py::arg("creg"),
+        py::arg("vm_lse") = c10::nullopt, py::arg("vm_logp") = c10::nullopt,
+        py::arg("vm_adv") = c10::nullopt, py::arg("vm_td") = c10::nullopt);
+  m.def("onpolicy_stats_fin", &onpolicy_stats_fin_hip,
+        "one-block reduce of the per-row loss partials into the stats vector",
+        py::arg("stats_part"), py::arg("stats"), py::arg("algo"),
+        py::arg("B"), py::arg("S"), py::arg("D"), py::arg("cp"),
+        py::arg("cv"), py::arg("ce"), py::arg("creg"));
+  m.def("vmpo_grad_rows", &vmpo_grad_rows_hip,
+        "V-MPO packed head grads from vmpo_mid's psi weights, one block per "
+        "batch row",
+        py::arg("outs"), py::arg("act"), py::arg("behav"), py::arg("vm_lse"),
+        py::arg("vm_psi"), py::arg("vm_td"), py::arg("vm_scalars"),
+        py::arg("gouts"), py::arg("cp"), py::arg("cv"), py::arg("creg"));
   m.def("vmpo_mid", &vmpo_mid_hip,
         "V-MPO cross-row middle kernel: selection + psi + duals + stats");
   m.def("gae", &gae_hip, "GAE reverse scan");
@@ -334,28 +305,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("rho_min"), pybind11::arg("c_bar"),
         pybind11::arg("vD") = 1, pybind11::arg("val_off") = 0,
         pybind11::arg("rew_scale") = 1.0);
-  m.def("cat_stats", &cat_stats_hip, "categorical log-softmax stats");
-  m.def("ppo_td_gae", &ppo_td_gae_hip, "fused TD target + GAE scan");
-  m.def("impala_loss_reduce", &impala_loss_reduce_hip, "IMPALA loss stats");
-  m.def("ppo_loss_reduce", &ppo_loss_reduce_hip, "PPO loss stats");
-  m.def("impala_loss_bwd", &impala_loss_bwd_hip, "analytic IMPALA loss grad");
-  m.def("ppo_loss_bwd", &ppo_loss_bwd_hip, "analytic PPO loss grad");
-  m.def("impala_loss_mega", &impala_loss_mega_hip,
-        "single-launch IMPALA loss: stats+vtrace+reduce+bwd");
-  m.def("ppo_loss_mega", &ppo_loss_mega_hip,
-        "single-launch PPO loss: stats+gae+reduce+bwd");
-  m.def("vmpo_loss_mega", &vmpo_loss_mega_hip,
-        "single-launch V-MPO loss: stats+gae+topk+duals+bwd",
-        py::arg("mo"), py::arg("act"), py::arg("behav"), py::arg("rew"),
-        py::arg("fir"), py::arg("log_eta"), py::arg("log_alpha"),
-        py::arg("gouts"), py::arg("g_eta"), py::arg("g_alpha"),
-        py::arg("stats"), py::arg("norm_sq"), py::arg("rng_state"),
-        py::arg("A"), py::arg("gamma"), py::arg("lmbda"),
-        py::arg("rew_scale"), py::arg("cp"), py::arg("cv"), py::arg("creg"),
-        py::arg("eps_eta"), py::arg("alpha_below"), py::arg("alpha_upper"),
-        py::arg("max_phase") = 99);
-  m.def("ppoc_loss_mega", &ppoc_loss_mega_hip,
-        "single-launch Gaussian-policy PPO loss (K5)");
   m.def("sac_actor_loss", &sac_actor_loss_hip,
         "SAC discrete actor+alpha loss with analytic grads",
         py::arg("moA"), py::arg("q1"), py::arg("q2"), py::arg("log_alpha"),

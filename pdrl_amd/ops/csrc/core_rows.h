@@ -1,8 +1,9 @@
 // Shared per-row device functions for the fused SeqLSTMCore kernels:
 // whole-sequence forward and BPTT backward for ONE batch row (= one
-// workgroup). Included by seq_lstm.hip (single/multi kernels) and
-// megastep.hip (whole-training-step kernels). Template definitions only —
-// ODR-safe across translation units.
+// workgroup). Included by seq_lstm.hip (single/multi kernels) and by the
+// kernels that fuse a loss phase into the row's launch (fwd_loss.hip,
+// sac_loss.hip, sacc_loss.hip). Template definitions only — ODR-safe across
+// translation units.
 #pragma once
 
 #include "common.h"

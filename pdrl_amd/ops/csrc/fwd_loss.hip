@@ -1,21 +1,30 @@
-// Forward+loss and backward+finalize fused launches for IMPALA / PPO.
+// Launches of the row-local on-policy losses (loss_row.h) for IMPALA / PPO /
+// PPO-Continuous / V-MPO.
 //
-// The on-policy losses are ROW-LOCAL (loss_row.h): after a block finishes
-// its row's forward it can compute that row's categorical stats,
-// V-trace/GAE scan and analytic head grads in the SAME launch — no grid
-// barrier, unlike the whole-step mega-kernel. The only cross-row products
-// are the monitoring sums: each row stores its partials, and block 0 of
-// the backward launch reduces them (stream order guarantees every row's
-// stores landed). This removes the dedicated single-block loss launch
-// (~9 µs of the 52.8 µs IMPALA step) without the megastep's barriers.
+// The on-policy losses are ROW-LOCAL: once a block has its row's forward
+// outputs it can compute that row's policy stats, V-trace/GAE scan and
+// analytic head grads with no grid barrier. The only cross-row products
+// are the monitoring sums: each row stores its partials, and ONE block of
+// a later launch reduces them (stream order guarantees every row's stores
+// landed).
+//
+// Two sets of launches run the same device functions:
+//   fused (H=64):  seq_lstm_fwd_loss = forward + loss phase per row;
+//                  seq_lstm_bwd_fin  = stats reduce in block 0 (V-MPO: the
+//                  row's grad emission) + BPTT per row. No dedicated loss
+//                  launch (~9 µs of the 52.8 µs IMPALA step).
+//   stand-alone (any H): onpolicy_loss_rows after seq_lstm_forward, then
+//                  onpolicy_stats_fin (V-MPO: vmpo_mid + vmpo_grad_rows),
+//                  then the ordinary seq_lstm_backward_core.
 //
 // Stats protocol (race-free by stream ordering, no barriers, no atomics):
-//   fwd_loss:  block 0 zeroes norm_sq (its next writer, the wgrad kernel,
-//              runs in a LATER launch); each row block PLAIN-stores its
-//              loss partials into its own stats_part row.
-//   bwd_fin:   block 0 reduces the (B, 8) partials in parallel and writes
-//              the final stats vector — nothing to re-zero (rows are
-//              fully overwritten every step).
+//   loss phase:    block 0 zeroes norm_sq (its next writer, the wgrad
+//                  kernel, runs in a LATER launch); each row block
+//                  PLAIN-stores its loss partials into its own stats_part
+//                  row.
+//   stats reduce:  one block reduces the (B, 8) partials in parallel and
+//                  writes the final stats vector — nothing to re-zero (rows
+//                  are fully overwritten every step).
 #include "common.h"
 #include "core_rows.h"
 #include "loss_row.h"
@@ -44,25 +53,52 @@ __global__ __launch_bounds__(4 * H) void seq_lstm_fwd_loss_kernel(
     float cv, float ce, float eps_clip, float creg) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   const int b = blockIdx.x;
-  if (b == 0 && threadIdx.x == 0 && norm_sq != nullptr) {
-    *norm_sq = 0.f;  // its next writer (wgrad) runs in a later launch
-  }
   seq_lstm_fwd_row<H>(x, h0, c0, body_w, body_b, w_ih, w_hh, b_g, heads_w,
                       heads_b, outs, hS, cS, stash, b, S, F, D, h0s,
                       smem_raw);
   __syncthreads();  // smem_raw reused by the loss phase
-  if (algo == 3) {  // V-MPO pre-phases: log-softmax + GAE to global scratch
-    vmpo_pre_row(outs, act, rew, fir, vm_lse, vm_logp, vm_adv, vm_td, b, S,
-                 D - 1, gamma, lmbda, rew_scale);
-  } else if (algo == 2) {  // PPO-Continuous (Gaussian tanh-mean policy)
-    ppoc_loss_row(outs, act, behav, rew, fir, gouts, stats_part, b, B, S,
-                  (D - 1) / 2, gamma, lmbda, rew_scale, cp, cv, ce,
-                  eps_clip, creg, smem_raw);
-  } else {
-    onpolicy_loss_row(algo, outs, act, behav, rew, fir, gouts, stats_part,
-                      b, B, S, D - 1, gamma, lmbda, rho_bar, rho_min, c_bar,
-                      rew_scale, cp, cv, ce, eps_clip, creg, smem_raw);
-  }
+  onpolicy_loss_phase(algo, outs, act, behav, rew, fir, gouts, stats_part,
+                      norm_sq, vm_lse, vm_logp, vm_adv, vm_td, b, B, S, D,
+                      gamma, lmbda, rho_bar, rho_min, c_bar, rew_scale, cp,
+                      cv, ce, eps_clip, creg, smem_raw);
+}
+
+// Stand-alone loss phase over the outputs of an ordinary seq_lstm_forward:
+// one block per batch row.
+__global__ __launch_bounds__(kLossThreads) void onpolicy_loss_rows_kernel(
+    const float* __restrict__ outs, const float* __restrict__ act,
+    const float* __restrict__ behav, const float* __restrict__ rew,
+    const float* __restrict__ fir, float* __restrict__ gouts,
+    float* __restrict__ stats_part, float* __restrict__ norm_sq,
+    float* __restrict__ vm_lse, float* __restrict__ vm_logp,
+    float* __restrict__ vm_adv, float* __restrict__ vm_td, int algo, int B,
+    int S, int D, float gamma, float lmbda, float rho_bar, float rho_min,
+    float c_bar, float rew_scale, float cp, float cv, float ce,
+    float eps_clip, float creg) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  onpolicy_loss_phase(algo, outs, act, behav, rew, fir, gouts, stats_part,
+                      norm_sq, vm_lse, vm_logp, vm_adv, vm_td, blockIdx.x, B,
+                      S, D, gamma, lmbda, rho_bar, rho_min, c_bar, rew_scale,
+                      cp, cv, ce, eps_clip, creg, smem_raw);
+}
+
+// Stand-alone stats reduce (IMPALA / PPO / PPO-C): ONE block.
+__global__ __launch_bounds__(kLossThreads) void onpolicy_stats_fin_kernel(
+    const float* __restrict__ stats_part, float* __restrict__ stats,
+    int algo, int B, int S, int D, float cp, float cv, float ce,
+    float creg) {
+  onpolicy_stats_reduce(stats_part, stats, algo, B, S, D, cp, cv, ce, creg);
+}
+
+// Stand-alone V-MPO grad emission after vmpo_mid: one block per batch row.
+__global__ __launch_bounds__(kLossThreads) void vmpo_grad_rows_kernel(
+    const float* __restrict__ outs, const float* __restrict__ act,
+    const float* __restrict__ behav, const float* __restrict__ vm_lse,
+    const float* __restrict__ vm_psi, const float* __restrict__ vm_td,
+    const float* __restrict__ vm_scalars, float* __restrict__ gouts, int B,
+    int S, int D, float cp, float cv, float creg) {
+  vmpo_grad_row(outs, act, behav, vm_lse, vm_psi, vm_td, vm_scalars, gouts,
+                blockIdx.x, B, S, D - 1, cp, cv, creg);
 }
 
 template <int H>
@@ -80,7 +116,7 @@ __global__ __launch_bounds__(4 * H) void seq_lstm_bwd_fin_kernel(
     float cp, float cv, float ce, float creg,
     const float* __restrict__ vm_outs) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  if (algo == 3) {
+  if (algo == kAlgoVmpo) {
     // V-MPO: emit this row's packed head grads from the middle kernel's
     // psi/scalars (stats already finalized there), then backward
     vmpo_grad_row(vm_outs, act, behav, vm_lse, vm_psi, vm_td, vm_scalars,
@@ -89,67 +125,17 @@ __global__ __launch_bounds__(4 * H) void seq_lstm_bwd_fin_kernel(
                   cv, creg);
     __syncthreads();
   } else if (blockIdx.x == 0) {
-    // parallel reduce the (B, 8) per-row loss partials (all written by
-    // the fwd_loss launch — stream order) and finalize the stats vector
-    const int tid = threadIdx.x;
-    float pl = 0.f, vl = 0.f, es = 0.f, rs = 0.f, rg = 0.f;
-    float rmn = 1e30f, rmx = -1e30f;
-    for (int b = tid; b < B; b += (int)blockDim.x) {
-      const float* sp = stats_part + (long)b * 8;
-      pl += sp[0];
-      vl += sp[1];
-      es += sp[2];
-      rs += sp[3];
-      rg += sp[4];
-      if (algo != kAlgoImpala) {  // PPO and PPO-C track ratio min/max
-        rmn = fminf(rmn, sp[5]);
-        rmx = fmaxf(rmx, sp[6]);
-      }
-    }
-#pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) {
-      pl += __shfl_down(pl, off, kWave);
-      vl += __shfl_down(vl, off, kWave);
-      es += __shfl_down(es, off, kWave);
-      rs += __shfl_down(rs, off, kWave);
-      rg += __shfl_down(rg, off, kWave);
-      rmn = fminf(rmn, __shfl_down(rmn, off, kWave));
-      rmx = fmaxf(rmx, __shfl_down(rmx, off, kWave));
-    }
-    __shared__ float s74[7][8];
-    const int lane = tid & (kWave - 1), wave = tid >> 6;
-    if (lane == 0) {
-      s74[0][wave] = pl; s74[1][wave] = vl; s74[2][wave] = es;
-      s74[3][wave] = rs; s74[4][wave] = rg; s74[5][wave] = rmn;
-      s74[6][wave] = rmx;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      const int nw = (int)blockDim.x / kWave;
-      float P = 0, V = 0, E = 0, R = 0, G2 = 0, MN = 1e30f, MX = -1e30f;
-      for (int w = 0; w < nw; ++w) {
-        P += s74[0][w]; V += s74[1][w]; E += s74[2][w];
-        R += s74[3][w]; G2 += s74[4][w];
-        MN = fminf(MN, s74[5][w]); MX = fmaxf(MX, s74[6][w]);
-      }
-      const int nlog = D - 1;  // regularized heads: A, or 2A for PPO-C
-      const float inv = 1.0f / (B * (S - 1));
-      stats[0] = cp * P * inv + cv * V * inv - ce * E * inv +
-                 creg * G2 * inv / nlog;
-      stats[1] = P * inv;
-      stats[2] = V * inv;
-      stats[3] = E * inv;
-      stats[4] = R * inv;
-      if (algo != kAlgoImpala) {
-        stats[5] = MN;
-        stats[6] = MX;
-      }
-    }
+    onpolicy_stats_reduce(stats_part, stats, algo, B, S, D, cp, cv, ce,
+                          creg);
     __syncthreads();  // s74 done before smem_raw phases start
   }
   seq_lstm_bwd_row<H>(gouts, nullptr, nullptr, stash, x, c0, body_w, w_ih,
                       w_hh, heads_w, nullptr, nullptr, nullptr, dgates, dxb,
                       blockIdx.x, S, F, D, h0s, smem_raw);
+}
+
+inline float* opt_ptr(const c10::optional<at::Tensor>& t) {
+  return t.has_value() ? t->data_ptr<float>() : nullptr;
 }
 
 }  // namespace
@@ -186,11 +172,8 @@ void seq_lstm_fwd_loss_hip(
       stash.data_ptr<float>(), act.data_ptr<float>(),
       behav.data_ptr<float>(), rew.data_ptr<float>(), fir.data_ptr<float>(),
       gouts.data_ptr<float>(), stats_part.data_ptr<float>(),
-      norm_sq.has_value() ? norm_sq->data_ptr<float>() : nullptr,
-      vm_lse.has_value() ? vm_lse->data_ptr<float>() : nullptr,
-      vm_logp.has_value() ? vm_logp->data_ptr<float>() : nullptr,
-      vm_adv.has_value() ? vm_adv->data_ptr<float>() : nullptr,
-      vm_td.has_value() ? vm_td->data_ptr<float>() : nullptr, (int)algo,
+      opt_ptr(norm_sq), opt_ptr(vm_lse), opt_ptr(vm_logp), opt_ptr(vm_adv),
+      opt_ptr(vm_td), (int)algo,
       B, S, F, D, (long)h0.stride(0), (float)gamma, (float)lmbda,
       (float)rho_bar, (float)rho_min, (float)c_bar, (float)rew_scale,
       (float)cp, (float)cv, (float)ce, (float)eps_clip, (float)creg);
@@ -223,15 +206,103 @@ void seq_lstm_bwd_fin_hip(
       w_ih.data_ptr<float>(), w_hh.data_ptr<float>(),
       heads_w.data_ptr<float>(), dgates.data_ptr<float>(),
       dxb.data_ptr<float>(), stats.data_ptr<float>(),
-      stats_part.data_ptr<float>(),
-      act.has_value() ? act->data_ptr<float>() : nullptr,
-      behav.has_value() ? behav->data_ptr<float>() : nullptr,
-      vm_lse.has_value() ? vm_lse->data_ptr<float>() : nullptr,
-      vm_psi.has_value() ? vm_psi->data_ptr<float>() : nullptr,
-      vm_td.has_value() ? vm_td->data_ptr<float>() : nullptr,
-      vm_scalars.has_value() ? vm_scalars->data_ptr<float>() : nullptr,
+      stats_part.data_ptr<float>(), opt_ptr(act), opt_ptr(behav),
+      opt_ptr(vm_lse), opt_ptr(vm_psi), opt_ptr(vm_td), opt_ptr(vm_scalars),
       (int)algo, B, S, F, D,
       (long)c0.stride(0), (float)cp, (float)cv, (float)ce, (float)creg,
-      vm_outs.has_value() ? vm_outs->data_ptr<float>() : nullptr);
+      opt_ptr(vm_outs));
+  HIP_CHECK_LAST();
+}
+
+// outs (B,S,D) from seq_lstm_forward → gouts + per-row stats partials
+// (V-MPO: the vm_* scratch consumed by vmpo_mid / vmpo_grad_rows).
+void onpolicy_loss_rows_hip(
+    const at::Tensor& outs, const at::Tensor& act, const at::Tensor& behav,
+    const at::Tensor& rew, const at::Tensor& fir, at::Tensor& gouts,
+    at::Tensor& stats_part, const c10::optional<at::Tensor>& norm_sq,
+    long algo, double gamma, double lmbda, double rho_bar, double rho_min,
+    double c_bar, double rew_scale, double cp, double cv, double ce,
+    double eps_clip, double creg, const c10::optional<at::Tensor>& vm_lse,
+    const c10::optional<at::Tensor>& vm_logp,
+    const c10::optional<at::Tensor>& vm_adv,
+    const c10::optional<at::Tensor>& vm_td) {
+  CHECK_IN(outs); CHECK_IN(act); CHECK_IN(behav); CHECK_IN(rew);
+  CHECK_IN(fir); CHECK_IN(gouts); CHECK_IN(stats_part);
+  TORCH_CHECK(outs.dim() == 3, "outs must be (B,S,D)");
+  const int B = outs.size(0), S = outs.size(1), D = outs.size(2);
+  const long N = (long)B * S;
+  TORCH_CHECK(S >= 2 && S <= kLossThreads,
+              "row-local loss gives one thread to each step: 2 <= S <= ",
+              kLossThreads);
+  TORCH_CHECK(algo >= kAlgoImpala && algo <= kAlgoVmpo, "unknown algo");
+  TORCH_CHECK(D >= (algo == kAlgoPpoC ? 3 : 2) &&
+                  (algo != kAlgoPpoC || D % 2 == 1),
+              "packed head width does not match the algorithm");
+  const long act_per = (algo == kAlgoPpoC) ? (D - 1) / 2 : 1;
+  TORCH_CHECK(act.numel() == N * act_per && behav.numel() == N &&
+                  rew.numel() == N && fir.numel() == N &&
+                  gouts.numel() == outs.numel() &&
+                  stats_part.numel() >= (long)B * 8,
+              "onpolicy_loss_rows: operand shapes do not match outs");
+  if (algo == kAlgoVmpo) {
+    TORCH_CHECK(vm_lse.has_value() && vm_logp.has_value() &&
+                    vm_adv.has_value() && vm_td.has_value(),
+                "V-MPO needs the vm_* scratch");
+    TORCH_CHECK(vm_lse->numel() >= N && vm_logp->numel() >= N &&
+                    vm_adv->numel() >= (long)B * (S - 1) &&
+                    vm_td->numel() >= (long)B * (S - 1),
+                "vm_* scratch too small");
+  }
+  hipLaunchKernelGGL(
+      onpolicy_loss_rows_kernel, dim3(B), dim3(kLossThreads),
+      6 * S * sizeof(float), current_stream(), outs.data_ptr<float>(),
+      act.data_ptr<float>(), behav.data_ptr<float>(), rew.data_ptr<float>(),
+      fir.data_ptr<float>(), gouts.data_ptr<float>(),
+      stats_part.data_ptr<float>(), opt_ptr(norm_sq), opt_ptr(vm_lse),
+      opt_ptr(vm_logp), opt_ptr(vm_adv), opt_ptr(vm_td), (int)algo, B, S, D,
+      (float)gamma, (float)lmbda, (float)rho_bar, (float)rho_min,
+      (float)c_bar, (float)rew_scale, (float)cp, (float)cv, (float)ce,
+      (float)eps_clip, (float)creg);
+  HIP_CHECK_LAST();
+}
+
+// (B,8) per-row partials → final stats vector (IMPALA / PPO / PPO-C).
+void onpolicy_stats_fin_hip(const at::Tensor& stats_part, at::Tensor& stats,
+                            long algo, long B, long S, long D, double cp,
+                            double cv, double ce, double creg) {
+  CHECK_IN(stats_part); CHECK_IN(stats);
+  TORCH_CHECK(B >= 1 && S >= 2 && D >= 2 && stats_part.numel() >= B * 8 &&
+                  stats.numel() >= 7,
+              "onpolicy_stats_fin: bad shapes");
+  hipLaunchKernelGGL(onpolicy_stats_fin_kernel, dim3(1), dim3(kLossThreads),
+                     0, current_stream(), stats_part.data_ptr<float>(),
+                     stats.data_ptr<float>(), (int)algo, (int)B, (int)S,
+                     (int)D, (float)cp, (float)cv, (float)ce, (float)creg);
+  HIP_CHECK_LAST();
+}
+
+// V-MPO packed head grads from vmpo_mid's psi weights and scalars.
+void vmpo_grad_rows_hip(const at::Tensor& outs, const at::Tensor& act,
+                        const at::Tensor& behav, const at::Tensor& vm_lse,
+                        const at::Tensor& vm_psi, const at::Tensor& vm_td,
+                        const at::Tensor& vm_scalars, at::Tensor& gouts,
+                        double cp, double cv, double creg) {
+  CHECK_IN(outs); CHECK_IN(act); CHECK_IN(behav); CHECK_IN(vm_lse);
+  CHECK_IN(vm_psi); CHECK_IN(vm_td); CHECK_IN(vm_scalars); CHECK_IN(gouts);
+  TORCH_CHECK(outs.dim() == 3, "outs must be (B,S,D)");
+  const int B = outs.size(0), S = outs.size(1), D = outs.size(2);
+  const long N = (long)B * S, BT = (long)B * (S - 1);
+  TORCH_CHECK(S >= 2 && D >= 2 && act.numel() == N &&
+                  behav.numel() == N * (D - 1) && vm_lse.numel() >= N &&
+                  vm_psi.numel() >= BT && vm_td.numel() >= BT &&
+                  vm_scalars.numel() >= 8 && gouts.numel() == outs.numel(),
+              "vmpo_grad_rows: operand shapes do not match outs");
+  hipLaunchKernelGGL(vmpo_grad_rows_kernel, dim3(B), dim3(kLossThreads), 0,
+                     current_stream(), outs.data_ptr<float>(),
+                     act.data_ptr<float>(), behav.data_ptr<float>(),
+                     vm_lse.data_ptr<float>(), vm_psi.data_ptr<float>(),
+                     vm_td.data_ptr<float>(), vm_scalars.data_ptr<float>(),
+                     gouts.data_ptr<float>(), B, S, D, (float)cp, (float)cv,
+                     (float)creg);
   HIP_CHECK_LAST();
 }

@@ -1,15 +1,21 @@
-// Row-local on-policy (IMPALA/PPO) loss for ONE batch row: categorical
-// stats, V-trace/GAE scan, analytic packed head grads, atomic loss-stat
-// partials. Shared by megastep.hip (whole-step kernel) and fwd_loss.hip
-// (loss fused into the forward launch): both exploit that these losses
-// have NO cross-row coupling except the monitoring means.
+// Row-local on-policy losses (IMPALA / PPO / PPO-Continuous / V-MPO) for ONE
+// batch row: policy stats, V-trace/GAE scan, analytic packed head grads,
+// per-row loss-stat partials. These are the ONLY implementation of the
+// on-policy loss math; fwd_loss.hip runs them either fused into the
+// forward/backward launches (H=64) or as stand-alone row-parallel launches
+// (any H). The losses have NO cross-row coupling except the monitoring
+// means (and V-MPO's top-half selection, vmpo_loss.hip).
 #pragma once
 
 #include "common.h"
 
 constexpr int kAlgoImpala = 0;
 constexpr int kAlgoPpo = 1;
-constexpr int kMsThreads = 256;
+constexpr int kAlgoPpoC = 2;
+constexpr int kAlgoVmpo = 3;
+// block size of the stand-alone launches; the row functions give one thread
+// to each of a row's S steps, so S <= kLossThreads (checked on the host)
+constexpr int kLossThreads = 256;
 
 __device__ __forceinline__ float ms_huber(float d) {
   const float a = fabsf(d);
@@ -21,12 +27,12 @@ __device__ __forceinline__ float ms_huber_grad(float d) {
 
 
 // Row-local IMPALA/PPO loss for batch row b: categorical stats, V-trace or
-// TD+GAE scan, analytic packed head grads, atomic loss-stat partials.
+// TD+GAE scan, analytic packed head grads, per-row loss-stat partials.
 // stats_part: (B, 8) per-row loss partials [pl, vl, es, ravg/rsum, rg,
 // rmin, rmax] written with PLAIN stores — a per-launch accumulator would
 // funnel 5-7 atomics per block onto one cache line, which measured ~10 µs
 // at B=128 (the whole benefit of fusing the loss into the forward). The
-// consumer (bwd_fin / megastep finalize) reduces the B rows in parallel.
+// consumer (onpolicy_stats_reduce below) reduces the B rows in parallel.
 __device__ void onpolicy_loss_row(
     int algo, const float* __restrict__ outs, const float* __restrict__ act,
     const float* __restrict__ behav, const float* __restrict__ rew,
@@ -179,8 +185,8 @@ __device__ void onpolicy_loss_row(
 
 
 // Row-local PPO-Continuous loss (Gaussian tanh-mean policy; reference math:
-// networks/models.py:103-118 + ppo/learning.py — identical numerics to
-// ppoc_loss.hip's mega kernel). Packed heads [mu | std | value], D = 2A+1.
+// networks/models.py:103-118 + ppo/learning.py). Packed heads
+// [mu | std | value], D = 2A+1.
 // Same per-row stats_part protocol as onpolicy_loss_row.
 __device__ inline void ppoc_loss_row(
     const float* __restrict__ outs, const float* __restrict__ act,
@@ -300,9 +306,9 @@ __device__ inline void ppoc_loss_row(
   }
 }
 
-// ---- V-MPO row-local phases (reference math: v_mpo/learning.py:49-124,
-// identical numerics to vmpo_loss.hip's mega kernel, which keeps only the
-// cross-row phases: top-half selection, psi softmax, dual losses, stats).
+// ---- V-MPO row-local phases (reference math: v_mpo/learning.py:49-124).
+// The cross-row phases — top-half selection, psi softmax, dual losses,
+// stats — run between them in vmpo_loss.hip's single-block vmpo_mid_kernel.
 
 // phases A+B for one row: log-softmax stats and the GAE scan, written to
 // GLOBAL scratch consumed by the single-block middle kernel.
@@ -385,5 +391,98 @@ __device__ inline void vmpo_grad_row(
     const float pb = __expf(zb[j] - lb);
     g[j] = dlogp * ((j == a ? 1.f : 0.f) - q) + alpha_v * (q - pb) * invBT +
            dreg * zq[j];
+  }
+}
+
+// ---- what a row's block runs once the row's forward outputs exist:
+// block 0 zeroes norm_sq (its next writer, the wgrad kernel, runs in a
+// LATER launch), then the algorithm's row-local loss phase. D is the packed
+// head width (A+1, or 2A+1 for PPO-C); smem holds 6*S floats.
+__device__ __forceinline__ void onpolicy_loss_phase(
+    int algo, const float* __restrict__ outs, const float* __restrict__ act,
+    const float* __restrict__ behav, const float* __restrict__ rew,
+    const float* __restrict__ fir, float* __restrict__ gouts,
+    float* __restrict__ stats_part, float* __restrict__ norm_sq,
+    float* __restrict__ vm_lse, float* __restrict__ vm_logp,
+    float* __restrict__ vm_adv, float* __restrict__ vm_td, int b, int B,
+    int S, int D, float gamma, float lmbda, float rho_bar, float rho_min,
+    float c_bar, float rew_scale, float cp, float cv, float ce,
+    float eps_clip, float creg, char* smem) {
+  if (b == 0 && threadIdx.x == 0 && norm_sq != nullptr) *norm_sq = 0.f;
+  if (algo == kAlgoVmpo) {  // log-softmax + GAE to global scratch
+    vmpo_pre_row(outs, act, rew, fir, vm_lse, vm_logp, vm_adv, vm_td, b, S,
+                 D - 1, gamma, lmbda, rew_scale);
+  } else if (algo == kAlgoPpoC) {  // Gaussian tanh-mean policy
+    ppoc_loss_row(outs, act, behav, rew, fir, gouts, stats_part, b, B, S,
+                  (D - 1) / 2, gamma, lmbda, rew_scale, cp, cv, ce,
+                  eps_clip, creg, smem);
+  } else {
+    onpolicy_loss_row(algo, outs, act, behav, rew, fir, gouts, stats_part,
+                      b, B, S, D - 1, gamma, lmbda, rho_bar, rho_min, c_bar,
+                      rew_scale, cp, cv, ce, eps_clip, creg, smem);
+  }
+}
+
+// ONE block: parallel reduce of the (B, 8) per-row loss partials (all
+// written by an EARLIER launch — stream order) into the final stats vector
+// of IMPALA / PPO / PPO-C. Nothing to re-zero: rows are fully overwritten
+// every step. Ends with its scratch still live — barrier before reusing LDS.
+__device__ __forceinline__ void onpolicy_stats_reduce(
+    const float* stats_part, float* stats,
+    int algo, int B, int S, int D, float cp, float cv, float ce,
+    float creg) {
+  const int tid = threadIdx.x;
+  float pl = 0.f, vl = 0.f, es = 0.f, rs = 0.f, rg = 0.f;
+  float rmn = 1e30f, rmx = -1e30f;
+  for (int b = tid; b < B; b += (int)blockDim.x) {
+    const float* sp = stats_part + (long)b * 8;
+    pl += sp[0];
+    vl += sp[1];
+    es += sp[2];
+    rs += sp[3];
+    rg += sp[4];
+    if (algo != kAlgoImpala) {  // PPO and PPO-C track ratio min/max
+      rmn = fminf(rmn, sp[5]);
+      rmx = fmaxf(rmx, sp[6]);
+    }
+  }
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+    pl += __shfl_down(pl, off, kWave);
+    vl += __shfl_down(vl, off, kWave);
+    es += __shfl_down(es, off, kWave);
+    rs += __shfl_down(rs, off, kWave);
+    rg += __shfl_down(rg, off, kWave);
+    rmn = fminf(rmn, __shfl_down(rmn, off, kWave));
+    rmx = fmaxf(rmx, __shfl_down(rmx, off, kWave));
+  }
+  __shared__ float s74[7][8];
+  const int lane = tid & (kWave - 1), wave = tid >> 6;
+  if (lane == 0) {
+    s74[0][wave] = pl; s74[1][wave] = vl; s74[2][wave] = es;
+    s74[3][wave] = rs; s74[4][wave] = rg; s74[5][wave] = rmn;
+    s74[6][wave] = rmx;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int nw = (int)blockDim.x / kWave;
+    float P = 0, V = 0, E = 0, R = 0, G2 = 0, MN = 1e30f, MX = -1e30f;
+    for (int w = 0; w < nw; ++w) {
+      P += s74[0][w]; V += s74[1][w]; E += s74[2][w];
+      R += s74[3][w]; G2 += s74[4][w];
+      MN = fminf(MN, s74[5][w]); MX = fmaxf(MX, s74[6][w]);
+    }
+    const int nlog = D - 1;  // regularized heads: A, or 2A for PPO-C
+    const float inv = 1.0f / (B * (S - 1));
+    stats[0] = cp * P * inv + cv * V * inv - ce * E * inv +
+               creg * G2 * inv / nlog;
+    stats[1] = P * inv;
+    stats[2] = V * inv;
+    stats[3] = E * inv;
+    stats[4] = R * inv;
+    if (algo != kAlgoImpala) {
+      stats[5] = MN;
+      stats[6] = MX;
+    }
   }
 }

@@ -1,5 +1,5 @@
 // Shared weight-gradient device bodies (MFMA gate GEMMs + wave-per-element
-// small grads) for wgrad.hip and megastep.hip. Template definitions only.
+// small grads) for wgrad.hip and sac_loss.hip. Template definitions only.
 #pragma once
 
 #include "common.h"

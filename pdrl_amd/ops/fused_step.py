@@ -2,23 +2,29 @@
 as a fixed HIP kernel DAG, bypassing autograd, with optional hipGraph
 capture.
 
-Default path for the H=64 family (_try_fwdloss, PDRL_FWDLOSS=1) — FOUR
-launches (47 µs/step, profiles/algo_breakdown_r02c.md):
-  1. seq_lstm_fwd_loss  — forward + the row-local loss (V-trace/GAE scans,
-                          analytic head grads, per-row stat partials); for
-                          V-MPO, the row-local log-softmax + GAE phases
-  2. [vmpo_mid]         — V-MPO only: slim single-block cross-row kernel
+The loss math has ONE implementation — the row-local device functions of
+csrc/loss_row.h (plus V-MPO's cross-row vmpo_mid) — reached by two launch
+sequences:
+
+Fused rows (H=64, the default; 47 µs/step, profiles/algo_breakdown_r02c.md):
+  1. seq_lstm_fwd_loss  — forward + the row's loss phase (V-trace/GAE scans,
+                          analytic head grads, per-row stat partials; for
+                          V-MPO, the log-softmax + GAE pre-phase)
+  2. [vmpo_mid]         — V-MPO only: single-block cross-row kernel
                           (radix-256 top-half selection, psi softmax,
-                          eta/alpha duals)
+                          eta/alpha duals, stats)
   3. seq_lstm_bwd_fin   — stat-partial reduce (block 0) + BPTT per row;
                           for V-MPO, the analytic grad emission per row
   4. seq_lstm_wgrad_out — MFMA weight-grad GEMMs written DIRECTLY into the
                           flat grad buffer's parameter views
-  5. l2norm_sq + rmsprop/adam — fused clip + update
+  5. rmsprop/adam       — fused clip + update
      [world > 1: RCCL all-reduce of the flat bucket before the update]
 
-Legacy sequence (PDRL_FWDLOSS=0 or H≠64): separate forward, mega loss
-kernel (or 4-kernel loss split beyond its LDS cap), backward, wgrad.
+Separate launches (H=32/128, or PDRL_FWDLOSS=0 at H=64): the same device
+functions behind their own thin launches —
+  seq_lstm_forward → onpolicy_loss_rows → onpolicy_stats_fin
+  (V-MPO: vmpo_mid → vmpo_grad_rows) → seq_lstm_backward_core
+— then steps 4-5 as above.
 
 No host syncs anywhere; stats are read back only at the log interval.
 With hipGraph capture (`use_graph`), the whole step replays as one graph
@@ -28,6 +34,7 @@ reference's ~hundreds of eager dispatches per iteration.
 """
 from __future__ import annotations
 
+import os
 import warnings
 
 import torch
@@ -42,6 +49,10 @@ _PPO_STATS = [
 _VMPO_STATS = ["loss-total", "loss-policy", "loss-value", "eta", "alpha", "kl"]
 
 BATCH_FIELDS = ["obs", "act", "rew", "logits", "log_prob", "is_fir", "hx", "cx"]
+
+_ALGO_ID = {"IMPALA": 0, "PPO": 1, "PPO-C": 2, "V-MPO": 3}  # csrc/loss_row.h
+_WGRAD_MAX_ROWS = 8192          # row-pointer table of the wgrad kernels (LDS)
+_VMPO_MID_LDS_BYTES = 56 * 1024  # vmpo_mid keeps s_adv + s_psi (BT each) in LDS
 
 
 class GraphableStep:
@@ -60,17 +71,31 @@ class GraphableStep:
     def _full(self, batch):  # implemented by subclasses
         raise NotImplementedError
 
-    def _try_capture(self, batch):
+    def _pin_and_warm(self, batch):
+        """Pin the caller's tensors as the graph inputs and run the step a
+        few times on a side stream (allocator + RCCL channel warmup)."""
         self._static = {k: batch[k] for k in BATCH_FIELDS}
         self._static_ptrs = {k: batch[k].data_ptr() for k in BATCH_FIELDS}
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                self._full(self._static)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+
+    def _restage(self, batch):
+        """Refresh the pinned graph inputs whose storage moved."""
+        for k in BATCH_FIELDS:
+            if batch[k].data_ptr() != self._static_ptrs[k]:
+                self._static[k].copy_(batch[k], non_blocking=True)
+
+    def _stats(self) -> dict:
+        return {name: self.stats_buf[i] for i, name in enumerate(self.stat_names)}
+
+    def _try_capture(self, batch):
         try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(3):  # warmup (allocator + RCCL channels)
-                    self._full(self._static)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
+            self._pin_and_warm(batch)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 self._full(self._static)
@@ -85,19 +110,21 @@ class GraphableStep:
         if self.use_graph and self._graph is None and not self._graph_failed:
             self._try_capture(batch)
         if self._graph is not None:
-            for k in BATCH_FIELDS:
-                if batch[k].data_ptr() != self._static_ptrs[k]:
-                    self._static[k].copy_(batch[k], non_blocking=True)
+            self._restage(batch)
             self._graph.replay()
         else:
             self._full(batch)
-        return {name: self.stats_buf[i] for i, name in enumerate(self.stat_names)}
+        return self._stats()
 
 
 class FusedOnPolicyStep(GraphableStep):
+    _ws_shape = None
+    _split_graphs = None
+    _split_failed = False
+
     def __init__(self, algo: str, core, params, optimizer, grad_reducer=None,
                  use_graph: bool = True, duals=None):
-        assert algo in ("IMPALA", "PPO", "V-MPO", "PPO-C")
+        assert algo in _ALGO_ID
         self.algo = algo
         self.core = core
         self.params = params
@@ -113,6 +140,10 @@ class FusedOnPolicyStep(GraphableStep):
             assert duals is not None
             self.rng_state = torch.randint(
                 1, 2**31 - 1, (1,), dtype=torch.int32, device=dev)
+        # fwd_loss / bwd_fin are specialized for the H=64 model family;
+        # PDRL_FWDLOSS=0 selects the separate launches there too
+        self.fused_rows = core.w_ih.size(0) == 64 and bool(
+            int(os.environ.get("PDRL_FWDLOSS", "1")))
         self.use_graph = use_graph
         self._graph = None
         self._static: dict[str, torch.Tensor] | None = None
@@ -120,8 +151,8 @@ class FusedOnPolicyStep(GraphableStep):
 
     # ------------------------------------------------------------------ #
     def _norm_buf(self):
-        """The optimizer's device-resident ||grad||² scalar (filled by the
-        loss-mega zero + wgrad accumulation in single-rank mode)."""
+        """The optimizer's device-resident ||grad||² scalar (zeroed by the
+        loss phase, accumulated by the wgrad kernels in single-rank mode)."""
         if self.grad_reducer is not None:
             return None  # post-allreduce norm is computed by optimizer.step()
         return self.optimizer.norm_sq
@@ -135,194 +166,150 @@ class FusedOnPolicyStep(GraphableStep):
         return [gs[2], gs[3], gs[0], gs[1], gs[4], gs[5], gs[6]]
 
     def fits(self, batch) -> bool:
-        """Whether a fused loss path covers this shape (V-MPO's
-        single-launch kernel has an LDS cap and no multi-kernel fallback;
-        IMPALA/PPO/PPO-C have shape-unlimited paths)."""
-        import os
-
+        """Whether the fused step covers this shape; updaters fall back to
+        eager autograd when it does not. The row-local losses have no shape
+        cap of their own."""
         B, S, _ = batch["obs"].shape
-        if B * S > 8192:
-            return False  # wgrad row-pointer table exceeds LDS
+        if B * S > _WGRAD_MAX_ROWS:
+            return False
         if self.algo == "V-MPO":
-            if self.core.w_ih.size(0) == 64 and bool(
-                    int(os.environ.get("PDRL_FWDLOSS", "1"))):
-                # split path: only the middle kernel's s_adv+s_psi in LDS
-                return 2 * B * (S - 1) * 4 <= 56 * 1024
-            return (2 * B * S + 3 * B * (S - 1)) * 4 <= 56 * 1024
-        if self.algo == "PPO-C":
-            if self.core.w_ih.size(0) == 64 and bool(
-                    int(os.environ.get("PDRL_FWDLOSS", "1"))):
-                return True  # row-local fwd+loss: no LDS shape limit
-            return (2 * B * S + 2 * B * (S - 1)) * 4 <= 56 * 1024
+            return 2 * B * (S - 1) * 4 <= _VMPO_MID_LDS_BYTES
         return True
 
-    def _loss(self, e, mo, act, behav, rew, fir, B, S, A, p):
-        """Loss stats + analytic head-grad buffer. One mega-kernel launch
-        when the shape fits a CU's LDS; 4-kernel sequence otherwise."""
-        gouts = torch.empty_like(mo)
-        norm = self._norm_buf()
-        creg = float(getattr(p, "logit_reg", 0.0))
-        if self.algo == "V-MPO":
-            log_eta, log_alpha = self.duals
-            ok = e.vmpo_loss_mega(
-                mo, act, self._behav_logits, rew, fir,
-                log_eta.data.view(1), log_alpha.data.view(1), gouts,
-                log_eta.grad.view(1), log_alpha.grad.view(1), self.stats_buf,
-                norm, self.rng_state, A, p.gamma, p.lmbda, p.reward_scale,
-                p.policy_loss_coef, p.value_loss_coef, creg, p.coef_eta,
-                p.coef_alpha_below, p.coef_alpha_upper,
-                max_phase=int(__import__("os").environ.get(
-                    "PDRL_VMPO_PHASE", "99")),  # profiling knob
-            )
-            if not ok:  # unreachable: updaters gate on fits() and fall back
-                raise RuntimeError(
-                    "vmpo_loss_mega refused a shape fits() accepted — "
-                    "fits() is out of sync with the kernel's LDS check")
-            if norm is None:
-                # multi-rank: eta/alpha grads are in the flat bucket already
-                pass
-            return gouts
-        if self.algo == "PPO-C":
-            ok = e.ppoc_loss_mega(
-                mo, act, behav, rew, fir, gouts, self.stats_buf, norm, A,
-                p.gamma, p.lmbda, p.reward_scale, p.policy_loss_coef,
-                p.value_loss_coef, p.entropy_coef, p.eps_clip, creg,
-            )
-            if not ok:  # unreachable: updaters gate on fits() and fall back
-                raise RuntimeError(
-                    "ppoc_loss_mega refused a shape fits() accepted — "
-                    "fits() is out of sync with the kernel's LDS check")
-            return gouts
-        if self.algo == "IMPALA":
-            if e.impala_loss_mega(
-                mo, act, behav, rew, fir, gouts, self.stats_buf, norm, A,
-                p.gamma, 0.8, 0.1, 1.0, p.reward_scale,
-                p.policy_loss_coef, p.value_loss_coef, p.entropy_coef, creg,
-            ):
-                return gouts
-            if norm is not None:
-                norm.zero_()  # fallback path: mega kernel didn't zero it
-            logp, ent, lse = e.cat_stats(mo, act, A)
-            logp2 = logp.view(B, S)
-            rhos, adv, vs = e.vtrace(
-                behav.view(B, S, 1), logp2.view(B, S, 1).contiguous(),
-                fir.view(B, S, 1), rew.view(B, S, 1), mo.view(B, S, -1),
-                p.gamma, 0.8, 0.1, 1.0, vD=mo.shape[-1], val_off=A,
-                rew_scale=p.reward_scale,
-            )
-            e.impala_loss_reduce(
-                logp2, ent.view(B, S), mo, A, adv, vs, rhos, self.stats_buf,
-                p.policy_loss_coef, p.value_loss_coef, p.entropy_coef, creg,
-            )
-            return e.impala_loss_bwd(
-                mo, A, act, lse, ent, adv, vs,
-                p.policy_loss_coef, p.value_loss_coef, p.entropy_coef, creg,
-            )
-        if e.ppo_loss_mega(
-            mo, act, behav, rew, fir, gouts, self.stats_buf, norm, A,
-            p.gamma, p.lmbda, p.reward_scale,
-            p.policy_loss_coef, p.value_loss_coef, p.entropy_coef, p.eps_clip,
-            creg,
-        ):
-            return gouts
-        if norm is not None:
-            norm.zero_()  # fallback path: mega kernel didn't zero it
-        logp, ent, lse = e.cat_stats(mo, act, A)
-        logp2 = logp.view(B, S)
-        td, adv = e.ppo_td_gae(rew, fir, mo, A, p.gamma, p.lmbda,
-                               p.reward_scale)
-        e.ppo_loss_reduce(
-            logp2, behav, ent.view(B, S), mo, A, adv, td, self.stats_buf,
-            p.policy_loss_coef, p.value_loss_coef, p.entropy_coef, p.eps_clip,
-            creg,
-        )
-        return e.ppo_loss_bwd(
-            mo, A, act, lse, ent, logp, behav.reshape(-1), adv, td,
-            p.policy_loss_coef, p.value_loss_coef, p.entropy_coef, p.eps_clip,
-            creg,
-        )
-
     def compute_grads_only(self, batch):
-        """Kernels 1-7 only (for gradient parity tests): fills the flat grad
-        buffer without touching the optimizer."""
+        """Everything but the optimizer (for gradient parity tests): fills
+        the flat grad buffer and the stats vector."""
         self._body(batch, update=False)
 
     # ------------------------------------------------------------------ #
-    def _mega_setup(self, batch):
-        """Workspaces for the whole-step mega-kernel (megastep.hip): all
-        intermediates + the grid-barrier state live in persistent device
-        buffers so ONE launch replays per step."""
+    def _workspace(self, B, S):
+        """Persistent device scratch for one (B, S): head grads, per-row
+        loss partials, V-MPO's inter-phase buffers and — fused rows only,
+        the separate launches allocate their own — the activations."""
+        if self._ws_shape == (B, S):
+            return self._ws
         c = self.core
-        x = batch["obs"]
-        B, S, _ = x.shape
-        dev = x.device
+        dev = c.body_w.device
         H = c.w_ih.size(0)
         D = c.heads_w.size(1)
 
         def mk(*shape):
             return torch.empty(*shape, device=dev)
 
-        self._ws = {
-            "outs": mk(B, S, D), "hS": mk(B, H), "cS": mk(B, H),
-            "stash": mk(B, S, 7 * H), "gouts": mk(B, S, D),
-            "dgates": mk(B, S, 4 * H), "dxb": mk(B, S, H),
-            "stats_part": mk(B, 8),
-            "bar": torch.zeros(1024, dtype=torch.int32, device=dev),
-        }
-        self._mega_shape = (B, S)
+        ws = {"gouts": mk(B, S, D),
+              "stats_part": mk(B, 8)}  # per-row loss partials (plain stores)
+        if self.algo == "V-MPO":
+            BT = B * (S - 1)
+            ws.update({
+                "vm_lse": mk(B * S), "vm_logp": mk(B * S),
+                "vm_adv": mk(BT), "vm_td": mk(BT), "vm_psi": mk(BT),
+                "vm_scalars": mk(8),
+            })
+        if self.fused_rows:
+            ws.update({
+                "outs": mk(B, S, D), "hS": mk(B, H), "cS": mk(B, H),
+                "stash": mk(B, S, 7 * H),
+                "dgates": mk(B, S, 4 * H), "dxb": mk(B, S, H),
+            })
+        self._ws, self._ws_shape = ws, (B, S)
+        return ws
 
-    def _try_megastep(self, e, batch, x, act, behav, rew, fir, hx0, cx0,
-                      B, S, A, p) -> bool:
-        """ONE kernel for the entire step (fwd+loss+bwd+wgrad+RMSprop with
-        in-kernel grid barriers). Single K_epoch, RMSprop-flat optimizers,
-        H=64 shapes that fit co-resident. Multi-rank runs the same kernel
-        WITHOUT the optimizer phase, then all-reduces + steps."""
-        import os
+    def _loss(self, e, batch, ws):
+        """Forward, loss and BPTT for every row: fills ws["gouts"] and the
+        stats vector; returns (stash, dgates, dxb) for the wgrad kernel."""
+        c, p = self.core, self.params
+        x = batch["obs"]
+        B, S, _ = x.shape
+        D = c.heads_w.size(1)
+        # strided row views (stride S*H) — the kernels take h0/c0 strides,
+        # so no .contiguous() copies here
+        hx0 = batch["hx"][:, 0]
+        cx0 = batch["cx"][:, 0]
+        act = batch["act"].reshape(-1)
+        rew = batch["rew"].reshape(B, S)
+        behav = batch["log_prob"].reshape(B, S)
+        fir = batch["is_fir"].reshape(B, S)
+        vmpo = self.algo == "V-MPO"
+        algo_i = _ALGO_ID[self.algo]
+        norm = self._norm_buf()
+        gouts, part = ws["gouts"], ws["stats_part"]
+        coefs = (p.policy_loss_coef, p.value_loss_coef, p.entropy_coef,
+                 float(getattr(p, "logit_reg", 0.0)))  # cp, cv, ce, creg
+        weights = (c.body_w, c.body_b, c.w_ih, c.w_hh, c.b_g, c.heads_w,
+                   c.heads_b)
+        bwd_weights = (c.body_w, c.w_ih, c.w_hh, c.heads_w)
+        loss_args = (act, behav, rew, fir, gouts, part, norm, algo_i,
+                     p.gamma, p.lmbda, 0.8, 0.1, 1.0, p.reward_scale,
+                     *coefs[:3], p.eps_clip, coefs[3])
+        pre = ({k: ws[k] for k in ("vm_lse", "vm_logp", "vm_adv", "vm_td")}
+               if vmpo else {})
 
-        if self.algo not in ("IMPALA", "PPO"):
-            return False
-        if p.K_epoch != 1:
-            return False
-        # OPT-IN (PDRL_MEGASTEP=1): measured 84 µs vs 52.6 µs for the
-        # multi-launch DAG at B=128/S=5 — the grid barrier costs 7.5 µs per
-        # use at 128 blocks (arrival atomics serialize on one line) and the
-        # combined kernel runs each phase a few µs slower than the
-        # specialized kernels (gpurun_out/mega_probe.log). Kept for larger
-        # shapes and as the 1-collective-per-step skeleton for multi-rank.
-        if not bool(int(os.environ.get("PDRL_MEGASTEP", "0"))):
-            return False
-        opt = self.optimizer
-        if not hasattr(opt, "sq_avg"):  # FusedRMSprop only
-            return False
-        if getattr(self, "_mega_shape", None) != (B, S):
-            self._mega_setup(batch)
-        ws = self._ws
-        c = self.core
-        gv = self._grad_views()  # [dw_ih, dw_hh, dbody_w, dbody_b, db_g, dheads_w, dheads_b]
-        single = self.grad_reducer is None
-        ok = e.megastep_onpolicy(
-            x, hx0, cx0, act, behav, rew, fir,
-            c.body_w, c.body_b, c.w_ih, c.w_hh, c.b_g, c.heads_w, c.heads_b,
-            ws["outs"], ws["hS"], ws["cS"], ws["stash"], ws["gouts"],
-            ws["dgates"], ws["dxb"], self.stats_buf, ws["stats_part"],
-            ws["bar"],
-            gv[0], gv[1], gv[2], gv[3], gv[4], gv[5], gv[6], opt.norm_sq,
-            opt.flat_param, opt.flat_grad, opt.sq_avg,
-            0 if self.algo == "IMPALA" else 1,
-            p.gamma, p.lmbda, 0.8, 0.1, 1.0, p.reward_scale,
-            p.policy_loss_coef, p.value_loss_coef, p.entropy_coef,
-            p.eps_clip, float(getattr(p, "logit_reg", 0.0)),
-            opt.lr, opt.alpha, opt.eps, opt.max_norm,
-            single,  # include_opt: single-rank updates in-kernel
-            int(os.environ.get("PDRL_MEGA_PHASE", "99")),  # profiling knob
-        )
-        if not ok:
-            return False
-        if not single:
-            # norm of the AVERAGED grads: all-reduce then clip+update
-            self.grad_reducer.all_reduce([opt.flat_grad])
-            opt.step()
-        return True
+        if self.fused_rows:
+            outs, stash = ws["outs"], ws["stash"]
+            e.seq_lstm_fwd_loss(x, hx0, cx0, *weights, outs, ws["hS"],
+                                ws["cS"], stash, *loss_args, **pre)
+        else:
+            outs, _, _, stash = e.seq_lstm_forward(x, hx0, cx0, *weights)
+            e.onpolicy_loss_rows(outs, *loss_args, **pre)
+
+        grad = {}
+        if vmpo:
+            behav_logits = batch["logits"].reshape(B * S, self.A)
+            log_eta, log_alpha = self.duals
+            if not e.vmpo_mid(
+                outs, behav_logits, ws["vm_logp"], ws["vm_lse"],
+                ws["vm_adv"], ws["vm_td"], log_eta.data.view(1),
+                log_alpha.data.view(1), ws["vm_psi"], ws["vm_scalars"],
+                log_eta.grad.view(1), log_alpha.grad.view(1), self.stats_buf,
+                norm, self.rng_state, self.A, coefs[0], coefs[1], coefs[3],
+                p.coef_eta, p.coef_alpha_below, p.coef_alpha_upper,
+            ):
+                raise RuntimeError(
+                    f"V-MPO batch ({B}, {S}) exceeds vmpo_mid's LDS; gate "
+                    "on fits() and fall back to the eager step")
+            grad = dict(act=act, behav=behav_logits, vm_lse=ws["vm_lse"],
+                        vm_psi=ws["vm_psi"], vm_td=ws["vm_td"],
+                        vm_scalars=ws["vm_scalars"])
+
+        if self.fused_rows:
+            dgates, dxb = ws["dgates"], ws["dxb"]
+            if vmpo:
+                grad["vm_outs"] = outs
+            e.seq_lstm_bwd_fin(gouts, stash, x, cx0, *bwd_weights, dgates,
+                               dxb, self.stats_buf, part, algo_i, *coefs,
+                               **grad)
+        else:
+            if vmpo:  # stats were finalized by vmpo_mid
+                e.vmpo_grad_rows(outs, gouts=gouts, cp=coefs[0], cv=coefs[1],
+                                 creg=coefs[3], **grad)
+            else:
+                e.onpolicy_stats_fin(part, self.stats_buf, algo_i, B, S, D,
+                                     *coefs)
+            _, _, _, dgates, dxb = e.seq_lstm_backward_core(
+                gouts, None, None, stash, x, cx0, *bwd_weights)
+        return hx0, stash, dgates, dxb
+
+    def _body(self, batch, update: bool = True):
+        e = ext()
+        x = batch["obs"]
+        ws = self._workspace(x.size(0), x.size(1))
+        hx0, stash, dgates, dxb = self._loss(e, batch, ws)
+        e.seq_lstm_wgrad_out(x, hx0, stash, dgates, dxb, ws["gouts"],
+                             *self._grad_views(), self._norm_buf())
+        if not update:
+            return
+        if self.grad_reducer is not None:
+            # multi-rank: norm must be of the AVERAGED grads → recompute
+            self.grad_reducer.all_reduce([self.optimizer.flat_grad])
+            self.optimizer.step()
+        else:
+            # single rank: ||grad||² was zeroed by the loss phase and
+            # accumulated by the wgrad kernels — skip fill + l2norm launches
+            self.optimizer._update()
+
+    def _full(self, batch):
+        for _ in range(self.params.K_epoch):
+            self._body(batch)
 
     # -- multi-rank split-graph: capture [fwd..wgrad] and [optimizer] as
     # two graphs with the RCCL all-reduce stream-ordered between them.
@@ -330,22 +317,11 @@ class FusedOnPolicyStep(GraphableStep):
     # cannot be validated on a single-GPU box; a bad replay would hang the
     # driver's one multi-GPU run, so the split is the default.
     def _try_capture_split(self, batch):
-        import os
-
-        self._split_graphs = None
         self._split_failed = True
         if self.params.K_epoch != 1:
             return
         try:
-            self._static = {k: batch[k] for k in BATCH_FIELDS}
-            self._static_ptrs = {k: batch[k].data_ptr() for k in BATCH_FIELDS}
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(3):  # warmup incl. RCCL channel setup
-                    self._full(self._static)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
+            self._pin_and_warm(batch)
             g_pre = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g_pre):
                 self._body(self._static, update=False)
@@ -361,177 +337,17 @@ class FusedOnPolicyStep(GraphableStep):
             self._static = None
 
     def run(self, batch) -> dict:
-        if self.grad_reducer is not None and self.use_graph and not bool(
-            int(__import__("os").environ.get("PDRL_GRAPH_RCCL", "0"))
-        ):
-            if getattr(self, "_split_graphs", None) is None and not getattr(
-                    self, "_split_failed", False):
-                self._try_capture_split(batch)
-            if getattr(self, "_split_graphs", None) is not None:
-                for k in BATCH_FIELDS:
-                    if batch[k].data_ptr() != self._static_ptrs[k]:
-                        self._static[k].copy_(batch[k], non_blocking=True)
-                g_pre, g_post = self._split_graphs
-                g_pre.replay()
-                self.grad_reducer.all_reduce([self.optimizer.flat_grad])
-                g_post.replay()
-                return {name: self.stats_buf[i]
-                        for i, name in enumerate(self.stat_names)}
+        if self.grad_reducer is None or not self.use_graph or bool(
+                int(os.environ.get("PDRL_GRAPH_RCCL", "0"))):
+            return super().run(batch)
+        if self._split_graphs is None and not self._split_failed:
+            self._try_capture_split(batch)
+        if self._split_graphs is None:
             self._full(batch)
-            return {name: self.stats_buf[i]
-                    for i, name in enumerate(self.stat_names)}
-        return super().run(batch)
-
-    # -- fwd+loss fusion: the on-policy loss is ROW-LOCAL, so it rides the
-    # forward launch (same block, no barrier) and the stats finalize at the
-    # head of the backward launch — removes the dedicated loss launch
-    # (~9 µs of the 52.8 µs step) with none of the megastep's barrier cost.
-    def _fwdloss_setup(self, batch):
-        c = self.core
-        x = batch["obs"]
-        B, S, _ = x.shape
-        dev = x.device
-        H = c.w_ih.size(0)
-        D = c.heads_w.size(1)
-
-        def mk(*shape):
-            return torch.empty(*shape, device=dev)
-
-        self._fl = {
-            "outs": mk(B, S, D), "hS": mk(B, H), "cS": mk(B, H),
-            "stash": mk(B, S, 7 * H), "gouts": mk(B, S, D),
-            "dgates": mk(B, S, 4 * H), "dxb": mk(B, S, H),
-            "stats_part": mk(B, 8),  # per-row loss partials (plain stores)
-        }
-        if self.algo == "V-MPO":
-            BT = B * (S - 1)
-            self._fl.update({
-                "vm_lse": mk(B * S), "vm_logp": mk(B * S),
-                "vm_adv": mk(BT), "vm_td": mk(BT), "vm_psi": mk(BT),
-                "vm_scalars": mk(8),
-            })
-        self._fl_shape = (B, S)
-
-    def _try_fwdloss(self, e, batch, x, act, behav, rew, fir, hx0, cx0,
-                     B, S, A, p, update) -> bool:
-        import os
-
-        if self.algo not in ("IMPALA", "PPO", "PPO-C", "V-MPO"):
-            return False
-        if self.core.w_ih.size(0) != 64:
-            return False  # kernels specialized for the H=64 model family
-        if not bool(int(os.environ.get("PDRL_FWDLOSS", "1"))):
-            return False
-        if self.algo == "V-MPO" and 2 * B * (S - 1) * 4 > 56 * 1024:
-            return False  # middle kernel's LDS cap (s_adv + s_psi)
-        if getattr(self, "_fl_shape", None) != (B, S):
-            self._fwdloss_setup(batch)
-        ws = self._fl
-        c = self.core
-        norm = self._norm_buf()
-        creg = float(getattr(p, "logit_reg", 0.0))
-        algo_i = {"IMPALA": 0, "PPO": 1, "PPO-C": 2, "V-MPO": 3}[self.algo]
-        vm = {}
-        if self.algo == "V-MPO":
-            vm = {"vm_lse": ws["vm_lse"], "vm_logp": ws["vm_logp"],
-                  "vm_adv": ws["vm_adv"], "vm_td": ws["vm_td"]}
-        e.seq_lstm_fwd_loss(
-            x, hx0, cx0, c.body_w, c.body_b, c.w_ih, c.w_hh, c.b_g,
-            c.heads_w, c.heads_b, ws["outs"], ws["hS"], ws["cS"],
-            ws["stash"], act, behav, rew, fir, ws["gouts"], ws["stats_part"],
-            norm, algo_i, p.gamma, p.lmbda, 0.8, 0.1, 1.0,
-            p.reward_scale, p.policy_loss_coef, p.value_loss_coef,
-            p.entropy_coef, p.eps_clip, creg, **vm,
-        )
-        if self.algo == "V-MPO":
-            log_eta, log_alpha = self.duals
-            ok = e.vmpo_mid(
-                ws["outs"], self._behav_logits, ws["vm_logp"], ws["vm_lse"],
-                ws["vm_adv"], ws["vm_td"], log_eta.data.view(1),
-                log_alpha.data.view(1), ws["vm_psi"], ws["vm_scalars"],
-                log_eta.grad.view(1), log_alpha.grad.view(1), self.stats_buf,
-                norm, self.rng_state, A, p.policy_loss_coef,
-                p.value_loss_coef, creg, p.coef_eta, p.coef_alpha_below,
-                p.coef_alpha_upper,
-            )
-            if not ok:  # unreachable: _try_fwdloss gates on the same cap
-                raise RuntimeError(
-                    "vmpo_mid refused a shape the python-side LDS gate "
-                    "accepted — the 2*BT*4 <= 56K checks are out of sync")
-            e.seq_lstm_bwd_fin(
-                ws["gouts"], ws["stash"], x, cx0, c.body_w, c.w_ih, c.w_hh,
-                c.heads_w, ws["dgates"], ws["dxb"], self.stats_buf,
-                ws["stats_part"], algo_i, p.policy_loss_coef,
-                p.value_loss_coef, p.entropy_coef, creg,
-                act=act, behav=self._behav_logits, vm_lse=ws["vm_lse"],
-                vm_psi=ws["vm_psi"], vm_td=ws["vm_td"],
-                vm_scalars=ws["vm_scalars"], vm_outs=ws["outs"],
-            )
         else:
-            e.seq_lstm_bwd_fin(
-                ws["gouts"], ws["stash"], x, cx0, c.body_w, c.w_ih, c.w_hh,
-                c.heads_w, ws["dgates"], ws["dxb"], self.stats_buf,
-                ws["stats_part"], algo_i, p.policy_loss_coef,
-                p.value_loss_coef, p.entropy_coef, creg,
-            )
-        e.seq_lstm_wgrad_out(x, hx0, ws["stash"], ws["dgates"], ws["dxb"],
-                             ws["gouts"], *self._grad_views(), norm)
-        if not update:
-            return True
-        if self.grad_reducer is not None:
+            self._restage(batch)
+            g_pre, g_post = self._split_graphs
+            g_pre.replay()
             self.grad_reducer.all_reduce([self.optimizer.flat_grad])
-            self.optimizer.step()
-        else:
-            self.optimizer._update()
-        return True
-
-    def _body(self, batch, update: bool = True):
-        c, p, A = self.core, self.params, self.A
-        e = ext()
-        x = batch["obs"]
-        B, S, _ = x.shape
-        # strided row views (stride S*H) — the kernels take h0/c0 strides,
-        # so no .contiguous() copies here
-        hx0 = batch["hx"][:, 0]
-        cx0 = batch["cx"][:, 0]
-        act = batch["act"].reshape(-1)
-        rew = batch["rew"].reshape(B, S)
-        behav = batch["log_prob"].reshape(B, S)
-        fir = batch["is_fir"].reshape(B, S)
-        if self.algo == "V-MPO":
-            self._behav_logits = batch["logits"].reshape(B * S, self.A)
-
-        if update and self._try_megastep(e, batch, x, act, behav, rew, fir,
-                                         hx0, cx0, B, S, A, p):
-            return
-        if self._try_fwdloss(e, batch, x, act, behav, rew, fir, hx0, cx0,
-                             B, S, A, p, update):
-            return
-
-        mo, hS, cS, stash = e.seq_lstm_forward(
-            x, hx0, cx0, c.body_w, c.body_b, c.w_ih, c.w_hh, c.b_g,
-            c.heads_w, c.heads_b,
-        )
-        gouts = self._loss(e, mo, act, behav, rew, fir, B, S, A, p)
-        _, _, _, dgates, dxb = e.seq_lstm_backward_core(
-            gouts, None, None, stash, x, cx0, c.body_w, c.w_ih, c.w_hh,
-            c.heads_w,
-        )
-        e.seq_lstm_wgrad_out(x, hx0, stash, dgates, dxb, gouts,
-                             *self._grad_views(), self._norm_buf())
-        if not update:
-            return
-        if self.grad_reducer is not None:
-            # multi-rank: norm must be of the AVERAGED grads → recompute
-            self.grad_reducer.all_reduce([self.optimizer.flat_grad])
-            self.optimizer.step()
-        else:
-            # single rank: ||grad||² was accumulated by the wgrad kernels
-            # (zeroed in the mega loss kernel) — skip fill + l2norm launches
-            self.optimizer._update()
-
-    def _full(self, batch):
-        for _ in range(self.params.K_epoch):
-            self._body(batch)
-
-
+            g_post.replay()
+        return self._stats()

@@ -21,14 +21,11 @@ SRC = [
     "pdrl_amd/ops/csrc/bindings.cpp",
     "pdrl_amd/ops/csrc/seq_lstm.hip",
     "pdrl_amd/ops/csrc/wgrad.hip",
-    "pdrl_amd/ops/csrc/losses.hip",
     "pdrl_amd/ops/csrc/vmpo_loss.hip",
-    "pdrl_amd/ops/csrc/ppoc_loss.hip",
     "pdrl_amd/ops/csrc/sac_loss.hip",
     "pdrl_amd/ops/csrc/sacc_loss.hip",
     "pdrl_amd/ops/csrc/scans.hip",
     "pdrl_amd/ops/csrc/multi_tensor.hip",
-    "pdrl_amd/ops/csrc/megastep.hip",
     "pdrl_amd/ops/csrc/fwd_loss.hip",
     "pdrl_amd/ops/csrc/rollout.hip",
 ]

@@ -123,52 +123,6 @@ def test_split_graph_multirank_path():
         assert abs(float(sa[k]) - float(sb[k])) < 1e-3, (k,)
 
 
-def test_megastep_matches_multilaunch():
-    """The whole-step mega-kernel (ONE launch: fwd+loss+bwd+wgrad+RMSprop
-    between grid barriers) must produce the same parameter trajectory and
-    stats as the multi-launch fused DAG, for both IMPALA and PPO."""
-    _ops()
-    import os
-
-    from pdrl_amd.agents.learner_module import switch_module
-    from pdrl_amd.utils import load_params
-    from tests.conftest import make_batch
-
-    for algo in ("IMPALA", "PPO"):
-        p = load_params()
-        p.algo = algo
-        p.batch_size, p.seq_len, p.obs_dim, p.n_actions = 32, 5, 4, 2
-        upd_cls, model_cls = switch_module(algo)
-
-        torch.manual_seed(21)
-        model_m = model_cls(4, 2, p.seq_len, p.hidden_size)
-        torch.manual_seed(21)
-        model_s = model_cls(4, 2, p.seq_len, p.hidden_size)
-
-        os.environ["PDRL_MEGASTEP"] = "1"
-        upd_m = upd_cls(model_m, p, DEV)
-        assert upd_m.fused_step is not None
-        upd_s = upd_cls(model_s, p, DEV)
-
-        batch = make_batch(p, seed=31, device=DEV)
-        try:
-            for _ in range(3):
-                os.environ["PDRL_MEGASTEP"] = "1"
-                sm = upd_m.step(batch)
-                os.environ["PDRL_MEGASTEP"] = "0"
-                ss = upd_s.step(batch)
-        finally:
-            os.environ.pop("PDRL_MEGASTEP", None)
-
-        fm = upd_m.optimizer.flat_param
-        fs = upd_s.optimizer.flat_param
-        torch.testing.assert_close(fm, fs, rtol=1e-4, atol=1e-6,
-                                   msg=lambda m: f"{algo} params: {m}")
-        for k in sm:
-            assert abs(float(sm[k]) - float(ss[k])) < 1e-3, (
-                algo, k, float(sm[k]), float(ss[k]))
-
-
 def test_dual_body_core_parity():
     """Dual-body SeqLSTMCore (continuous-critic topology: obs/action
     encoders straight into the LSTM): fused forward AND full autograd
@@ -464,14 +418,14 @@ def test_fused_grad_parity_vs_autograd(algo):
 
 
 @pytest.mark.parametrize("bsz,fwdloss", [
-    (16, "1"), (16, "0"),   # split-phase path vs mega-kernel path
-    (1024, "1"),            # split path beyond the mega kernel's LDS cap
+    (16, "1"), (16, "0"),   # fused rows vs separate launches
+    (1024, "1"),            # BT=4096: vmpo_mid's multi-pass strided loops
 ])
 def test_vmpo_fused_grad_parity_vs_autograd(bsz, fwdloss):
     """Fused V-MPO loss (top-half selection + duals + analytic bwd) vs GPU
     eager autograd, with the sampled dual coefficient pinned. Covers both
-    the split-phase path (row-local pre/grad fused into the fwd/bwd
-    launches, PDRL_FWDLOSS=1) and the legacy single mega kernel."""
+    launch sequences: row-local pre/grad phases fused into the fwd/bwd
+    launches (PDRL_FWDLOSS=1) and the separate launches (PDRL_FWDLOSS=0)."""
     _ops()
     import os
 
@@ -604,10 +558,10 @@ def test_fused_impala_shape_sweep(B, S, A):
 
 
 def test_fused_impala_large_shape_fallback():
-    """Large shapes, BOTH fused paths vs eager autograd: the fwd+loss
-    fused launch (row-local, no shape cap) and — with PDRL_FWDLOSS=0 —
-    the legacy route where the mega loss kernel exceeds its LDS budget
-    and falls back to the 4-kernel loss sequence."""
+    """Large shapes, BOTH launch sequences vs eager autograd: the loss
+    fused into the forward launch and — with PDRL_FWDLOSS=0 — the
+    separate forward / loss / backward launches. The row-local loss has
+    no shape cap on either."""
     _ops()
     import os
 
@@ -637,6 +591,131 @@ def test_fused_impala_large_shape_fallback():
                     msg=lambda m: f"fwdloss={fwdloss} {n}: {m}")
         finally:
             os.environ.pop("PDRL_FWDLOSS", None)
+
+
+def _onpolicy_updater(algo, hidden, bsz, seq, n_act=2, seed=3):
+    """(updater, batch) of an on-policy algorithm on the GPU, with V-MPO's
+    sampled dual coefficient pinned."""
+    from pdrl_amd.agents.learner_module import switch_module
+    from pdrl_amd.utils import load_params
+    from tests.conftest import make_batch
+
+    continuous = algo.endswith("Continuous")
+    p = load_params()
+    p.algo = algo
+    p.batch_size, p.seq_len, p.hidden_size = bsz, seq, hidden
+    p.obs_dim = 2 if continuous else 4
+    p.n_actions = 1 if continuous else n_act
+    p.coef_alpha_below = p.coef_alpha_upper = 0.0075
+    upd_cls, model_cls = switch_module(algo)
+    torch.manual_seed(seed)
+    model = model_cls(p.obs_dim, p.n_actions, seq, hidden)
+    upd = upd_cls(model, p, DEV)
+    batch = make_batch(p, n_actions=p.n_actions, continuous=continuous,
+                       device=DEV, seed=seed + 40)
+    return upd, batch
+
+
+def _assert_fused_grads_match_autograd(upd, batch, rtol, atol, tag):
+    """compute_grads_only vs compute_losses().backward() on the same GPU."""
+    fs = upd.fused_step
+    assert fs is not None and fs.fits(batch)
+    named = list(upd.model.named_parameters())
+    duals = list(upd.extra_params().items())  # V-MPO: log_eta, log_alpha
+
+    fs.compute_grads_only(batch)
+    fused = {n: q.grad.detach().clone() for n, q in named + duals}
+    upd.optimizer.zero_grad()
+    loss, _ = upd.compute_losses(batch)
+    loss.backward()
+    for n, q in named:
+        torch.testing.assert_close(fused[n], q.grad, rtol=rtol, atol=atol,
+                                   msg=lambda m: f"{tag} {n}: {m}")
+    for n, q in duals:
+        torch.testing.assert_close(fused[n].squeeze(), q.grad.squeeze(),
+                                   rtol=1e-3, atol=1e-5,
+                                   msg=lambda m: f"{tag} {n}: {m}")
+
+
+@pytest.mark.parametrize("algo,hidden,bsz,seq,n_act", [
+    (algo, hidden, 3, 3, 2)
+    for algo in ("IMPALA", "PPO", "PPO-Continuous", "V-MPO")
+    for hidden in (32, 128)
+] + [
+    (algo, 32, bsz, seq, n_act)
+    for algo in ("IMPALA", "PPO")
+    # (1, 2): T=1, a one-step scan with BT=1; (7, 8, 5): odd sizes
+    for bsz, seq, n_act in ((1, 2, 2), (7, 8, 5))
+])
+def test_general_path_grad_parity_vs_autograd(algo, hidden, bsz, seq, n_act):
+    """H≠64 runs the row-local losses as separate launches (forward,
+    loss rows, stats reduce / V-MPO mid + grad rows, backward): gradients
+    must match GPU eager autograd for every algorithm."""
+    _ops()
+    upd, batch = _onpolicy_updater(algo, hidden, bsz, seq, n_act)
+    assert not upd.fused_step.fused_rows
+    _assert_fused_grads_match_autograd(
+        upd, batch, rtol=2e-4, atol=2e-6,
+        tag=f"{algo} H={hidden} {(bsz, seq, n_act)}")
+
+
+@pytest.mark.parametrize("fwdloss", ["1", "0"])
+@pytest.mark.parametrize("algo", ["IMPALA", "PPO", "PPO-Continuous", "V-MPO"])
+def test_fused_stats_match_eager(algo, fwdloss):
+    """Every stat the fused step reports (the per-row partials + one-block
+    reduce, or vmpo_mid's) vs the eager loss, on both launch sequences."""
+    _ops()
+    import os
+
+    os.environ["PDRL_FWDLOSS"] = fwdloss
+    try:
+        upd, batch = _onpolicy_updater(algo, 64, 16, 5)
+    finally:
+        os.environ.pop("PDRL_FWDLOSS", None)
+    fs = upd.fused_step
+    assert fs is not None and fs.fits(batch)
+    assert fs.fused_rows == (fwdloss == "1")
+
+    fs._body(batch, update=False)
+    got = {n: fs.stats_buf[i].clone() for i, n in enumerate(fs.stat_names)}
+    _, want = upd.compute_losses(batch)
+    shared = [n for n in fs.stat_names if n in want]
+    must = {"V-MPO": {"eta", "alpha", "kl"},
+            "IMPALA": {"rho-avg"}}.get(algo, {"ratio-min", "ratio-max"})
+    assert must | {"loss-total", "loss-policy", "loss-value"} <= set(shared)
+    for n in shared:
+        torch.testing.assert_close(
+            got[n], want[n].detach().float().reshape(()), rtol=1e-3,
+            atol=1e-4, msg=lambda m: f"{algo} fwdloss={fwdloss} {n}: {m}")
+
+
+@pytest.mark.parametrize("algo", ["PPO-Continuous", "V-MPO"])
+def test_fused_path_width_beyond_old_loss_cap(algo):
+    """B=1024, S=5 at H=32: beyond the (2BS+2BT)*4 / (2BS+3BT)*4 <= 56 KiB
+    LDS caps the single-block loss kernels had; the row-local losses only
+    keep vmpo_mid's 2*BT*4 cap and the wgrad row table (B*S <= 8192)."""
+    _ops()
+    upd, batch = _onpolicy_updater(algo, 32, 1024, 5)
+    _assert_fused_grads_match_autograd(upd, batch, rtol=1e-3, atol=2e-5,
+                                       tag=f"{algo} B=1024")
+
+
+def test_impala_gates_on_fits_beyond_wgrad_table():
+    """B*S > 8192 exceeds the wgrad kernels' row-pointer table: IMPALA must
+    see fits() == False (and so take the eager step), like the others."""
+    _ops()
+    upd, batch = _onpolicy_updater("IMPALA", 64, 2048, 5)
+    assert upd.fused_step is not None
+    assert not upd.fused_step.fits(batch)
+
+    def no_launch(_batch):
+        raise AssertionError("fused step launched on a shape fits() rejects")
+
+    upd.fused_step.run = no_launch
+    stats = upd.step(batch)  # the eager step
+    assert all(np.isfinite(float(v)) for v in stats.values()), stats
+    upd_ok, batch_ok = _onpolicy_updater("IMPALA", 64, 1638, 5)  # 8190 rows
+    assert upd_ok.fused_step.fits(batch_ok)
 
 
 @pytest.mark.parametrize("fast8", ["1", "0"])
