@@ -15,8 +15,9 @@ MI355X-first differences:
   GradReducer (reference has a single-GPU learner only);
 * batch staging goes through a pinned-host buffer + async H2D copy
   (BatchStager below) instead of per-field blocking copies;
-* device actor mode (``"actor_mode": "device"``): for native envs with
-  discrete policies the learner rolls out on the GPU itself
+* device actor mode (``"actor_mode": "device"``): for envs with device
+  dynamics (CartPole-v1 with a discrete policy, MountainCarContinuous-v0
+  with a Gaussian one) the learner rolls out on the GPU itself
   (ops/rollout.py) and needs no ring, storage, manager or workers — see
   ``Learner._init_device_actor``. Env state is not checkpointed.
 """
@@ -308,28 +309,49 @@ class Learner:
         process, H2D staging or weight broadcast (the PUB socket is not
         bound), and the data is exactly on-policy: ``log_prob`` / ``logits``
         come from the weights the update is about to use. On-policy algos
-        train on the rollout itself; discrete SAC appends it to the
-        ``DeviceReplay`` and samples. The ring is never read or written.
+        train on the rollout itself; SAC (discrete and continuous) appends
+        it to the ``DeviceReplay`` and samples. The policy kind must match
+        the env's action space. The ring is never read or written.
         Env state is not checkpointed: a resumed run starts fresh episodes.
         """
-        from pdrl_amd.ops.rollout import DeviceRollout, has_device_env
+        from pdrl_amd.ops.rollout import (DeviceRollout, has_device_env,
+                                          is_continuous_env)
 
         p = self.params
-        if p.algo.endswith("Continuous") or getattr(p, "continuous", False):
-            raise ValueError(
-                f"actor_mode='device' supports discrete policies only "
-                f"(algo {p.algo!r} is continuous); use actor_mode='workers'")
+        continuous_algo = (p.algo.endswith("Continuous")
+                           or bool(getattr(p, "continuous", False)))
         if not has_device_env(p.env):
             raise ValueError(
                 f"actor_mode='device': env {p.env!r} has no device dynamics; "
                 f"use actor_mode='workers'")
+        if continuous_algo and not is_continuous_env(p.env):
+            raise ValueError(
+                f"actor_mode='device' on env {p.env!r} supports discrete "
+                f"policies only (algo {p.algo!r} is continuous); use a "
+                f"continuous-action device env or actor_mode='workers'")
+        if not continuous_algo and is_continuous_env(p.env):
+            raise ValueError(
+                f"actor_mode='device' on env {p.env!r} supports continuous "
+                f"policies only (algo {p.algo!r} is discrete); use a "
+                f"discrete-action device env or actor_mode='workers'")
         mods = self.updater.trainable_modules()
         m = mods.get("model") or next(iter(mods.values()))
         actor = getattr(m, "actor", m)
         n_envs = int(getattr(p, "device_envs", 0) or 0) or p.batch_size
+        # OU exploration (continuous, off-policy only — on-policy importance
+        # ratios assume policy actions, the rule of agents/worker.py): the
+        # first explore_ou_envs envs explore forever, every env does for its
+        # first explore_warmup_steps ticks
+        explore = {}
+        if continuous_algo and not self.on_policy:
+            explore = dict(
+                ou_envs=min(int(getattr(p, "explore_ou_envs", 0) or 0), n_envs),
+                warmup_steps=int(getattr(p, "explore_warmup_steps", 0) or 0),
+                ou_theta=float(getattr(p, "explore_ou_theta", 0.15)),
+                ou_sigma=float(getattr(p, "explore_ou_sigma", 0.6)))
         self.device_rollout = DeviceRollout(
             actor.core, p.env, n_envs, p.seq_len, self.device,
-            seed=1234 + self.rank, time_horizon=p.time_horizon)
+            seed=1234 + self.rank, time_horizon=p.time_horizon, **explore)
         self.is_root = self.rank == 0
         self.device_replay = None
         if not self.on_policy:

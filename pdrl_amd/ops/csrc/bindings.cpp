@@ -41,6 +41,13 @@ void rollout_discrete_hip(
     at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
     at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, long,
     long, long, long);
+void rollout_gaussian_hip(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, at::Tensor&,
+    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+    at::Tensor&, long, long, long, long, long, long, long, double, double);
 double rollout_uniform_host(long, long, long, long);
 void seq_lstm_fwd_loss_hip(
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
@@ -243,6 +250,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("log_prob"), py::arg("is_fir_out"), py::arg("hx"),
         py::arg("cx"), py::arg("ep_ret"), py::arg("env_id"), py::arg("seed"),
         py::arg("time_horizon"), py::arg("max_episode_steps"));
+  m.def("rollout_gaussian", &rollout_gaussian_hip,
+        "device actor for continuous control: rollout_discrete's contract "
+        "with a Gaussian policy (mode 0 = PPO-C, 1 = SAC-C + OU exploration)",
+        py::arg("body_w"), py::arg("body_b"), py::arg("w_ih"), py::arg("w_hh"),
+        py::arg("b_g"), py::arg("heads_w"), py::arg("heads_b"),
+        py::arg("env_state"), py::arg("h"), py::arg("c"), py::arg("is_fir"),
+        py::arg("ep_steps"), py::arg("ep_run"), py::arg("tick"),
+        py::arg("ou_state"), py::arg("obs"), py::arg("act"), py::arg("rew"),
+        py::arg("logits"), py::arg("log_prob"), py::arg("is_fir_out"),
+        py::arg("hx"), py::arg("cx"), py::arg("ep_ret"), py::arg("env_id"),
+        py::arg("mode"), py::arg("seed"), py::arg("time_horizon"),
+        py::arg("max_episode_steps"), py::arg("ou_envs"),
+        py::arg("warmup_steps"), py::arg("ou_theta"), py::arg("ou_sigma"));
   m.def("rollout_uniform", &rollout_uniform_host,
         "host evaluation of the rollout's counter-hash uniform",
         py::arg("seed"), py::arg("env"), py::arg("tick"), py::arg("k"));

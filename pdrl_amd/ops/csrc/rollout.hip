@@ -5,7 +5,10 @@
 // straight into persistent device tensors: policy forward, categorical
 // sample, log-prob, env dynamics, termination and auto-reset never leave the
 // GPU. The single-call CPU counterpart is cpu_actor.cpp::act_batch_discrete;
-// the eager oracle is pdrl_amd/ops/rollout.py.
+// the eager oracle is pdrl_amd/ops/rollout.py. rollout_gaussian (below) is the
+// continuous-control sibling: same geometry and recurrent part, a Gaussian
+// policy (PPO-C / SAC-C sampling schemes of cpu_actor.cpp::act_batch_gaussian)
+// and a float action.
 //
 // Geometry: as seq_lstm_fwd_row (core_rows.h) — one 4H-thread workgroup per
 // environment, thread = gate column with its w_ih / w_hh column resident in
@@ -78,6 +81,48 @@ struct CartPoleDyn {
   }
 };
 
+// Continuous-action envs have their own traits interface: kObsDim, kActDim,
+// kResetDraws (hash lanes 1..kResetDraws feed reset), drift(state) — the part
+// of the update that does not depend on the action, so another wave can
+// evaluate it while the policy heads are still being reduced — and
+// step(state, action, drift, reward, terminated) with a float action. Only
+// the sampled action is stepped (there is no "every action" to enumerate).
+
+// MountainCarContinuous-v0: constants and update of
+// pdrl_amd/envs/mountain_car.py, fp32, in the op order of the oracle
+// (MountainCarContDyn in pdrl_amd/ops/rollout.py); explicit mul / add / sub so
+// no fma contraction moves a trajectory across the wall or goal tests.
+struct MountainCarContDyn {
+  static constexpr int kObsDim = 2;
+  static constexpr int kActDim = 1;
+  static constexpr int kResetDraws = 1;
+
+  __device__ static void reset(float* s, const float* u) {
+    s[0] = __fadd_rn(-0.6f, __fmul_rn(0.2f, u[0]));
+    s[1] = 0.0f;
+  }
+
+  __device__ static float drift(const float* s) {
+    return __fmul_rn(0.0025f, cosf(__fmul_rn(3.0f, s[0])));
+  }
+
+  __device__ static void step(float* s, float a, float drift, float& reward,
+                              bool& terminated) {
+    const float force = fminf(fmaxf(a, -1.0f), 1.0f);
+    float vel =
+        __fadd_rn(s[1], __fsub_rn(__fmul_rn(force, 0.0015f), drift));
+    vel = fminf(fmaxf(vel, -0.07f), 0.07f);
+    const float raw = __fadd_rn(s[0], vel);
+    const float pos = fminf(fmaxf(raw, -1.2f), 0.6f);
+    if (pos <= -1.2f && vel < 0.0f) vel = 0.0f;
+    terminated = pos >= 0.45f && vel >= 0.0f;
+    reward = __fadd_rn(__fmul_rn(__fmul_rn(-0.1f, force), force),
+                       terminated ? 100.0f : 0.0f);
+    s[0] = pos;
+    s[1] = vel;
+  }
+};
+
 struct RolloutArgs {
   // live policy weights (transposed layout, read by pointer every launch)
   const float* body_w;   // (F, H)
@@ -110,85 +155,60 @@ struct RolloutArgs {
   int time_horizon, max_episode_steps;
 };
 
-template <int H, typename Env>
-__global__ __launch_bounds__(4 * H) void rollout_discrete(RolloutArgs p) {
-  constexpr int G = 4 * H;
-  constexpr int F = Env::kObsDim;
-  constexpr int A = Env::kActions;
-  const int tid = threadIdx.x;
-  const int n = blockIdx.x;
-  if (n >= p.N) return;  // uniform per workgroup
-
-  __shared__ __attribute__((aligned(16))) float s_xb[H];
-  __shared__ __attribute__((aligned(16))) float s_h[H];
-  __shared__ __attribute__((aligned(16))) float s_c[H];
-  __shared__ __attribute__((aligned(16))) float s_gates[G];
-  __shared__ float s_hw[A * H];  // logits head columns, [a][k]
-  __shared__ float s_obs[F];
-  __shared__ float s_cand[A * F];  // next state for every action
-  __shared__ float s_crew[A];
-  __shared__ int s_cterm[A];
-  __shared__ float s_ur[4];  // reset uniforms of this tick
-  __shared__ float s_fir;
-  __shared__ int s_reset;
-
+// ---- recurrent part, shared by rollout_discrete and rollout_gaussian ------
+// Thread tid of the 4H-thread workgroup owns gate column tid (and, for
+// tid < H, body column tid). load() runs once per launch, step() once per env
+// step; everything is force-inlined so the weight columns stay in the calling
+// kernel's VGPRs.
+template <int H, int F>
+struct RecurrentCore {
+  static constexpr int G = 4 * H;
   // Register-resident gate weight columns (thread = gate column tid). A
   // 4H-thread workgroup has a 256-VGPR budget per thread, which holds both
   // columns (2H values) only up to H = 64; at H = 128 the w_hh column stays
   // in registers and the w_ih column is streamed per step (coalesced,
   // L2-resident, S·H loads per thread) — no scratch in either case.
-  constexpr bool kWihRegs = H <= 64;
-  constexpr int HW = kWihRegs ? H : 4;
+  static constexpr bool kWihRegs = H <= 64;
+  static constexpr int HW = kWihRegs ? H : 4;
   float wih[HW], whh[H];
-  if constexpr (kWihRegs) {
-#pragma unroll
-    for (int k = 0; k < H; ++k) wih[k] = p.w_ih[k * G + tid];
-    PDRL_PIN_REGS(wih, H);
-  }
-#pragma unroll
-  for (int k = 0; k < H; ++k) whh[k] = p.w_hh[k * G + tid];
-  PDRL_PIN_REGS(whh, H);
-  const float bias = p.b_g[tid];
-  float hb[A];
-#pragma unroll
-  for (int a = 0; a < A; ++a) hb[a] = p.heads_b[a];
+  float bias;
+  float bw[F];  // body column of thread j < H (F is a handful of values)
+  float bb;
 
-  // body column of thread j < H (F is a handful of values)
-  float bw[F];
-  float bb = 0.0f;
-  if (tid < H) {
+  // Weight columns into registers; env n's carried h / c into LDS.
+  __device__ __forceinline__ void load(const RolloutArgs& p, int tid, int n,
+                                       float* s_h, float* s_c) {
+    if constexpr (kWihRegs) {
 #pragma unroll
-    for (int k = 0; k < F; ++k) bw[k] = p.body_w[k * H + tid];
-    bb = p.body_b[tid];
-    s_h[tid] = p.h[(long)n * H + tid];
-    s_c[tid] = p.c[(long)n * H + tid];
-  } else {
+      for (int k = 0; k < H; ++k) wih[k] = p.w_ih[k * G + tid];
+      PDRL_PIN_REGS(wih, H);
+    }
 #pragma unroll
-    for (int k = 0; k < F; ++k) bw[k] = 0.0f;
+    for (int k = 0; k < H; ++k) whh[k] = p.w_hh[k * G + tid];
+    PDRL_PIN_REGS(whh, H);
+    bias = p.b_g[tid];
+    bb = 0.0f;
+    if (tid < H) {
+#pragma unroll
+      for (int k = 0; k < F; ++k) bw[k] = p.body_w[k * H + tid];
+      bb = p.body_b[tid];
+      s_h[tid] = p.h[(long)n * H + tid];
+      s_c[tid] = p.c[(long)n * H + tid];
+    } else {
+#pragma unroll
+      for (int k = 0; k < F; ++k) bw[k] = 0.0f;
+    }
   }
-  for (int idx = tid; idx < A * H; idx += G) {
-    const int a = idx / H, k = idx % H;
-    s_hw[idx] = p.heads_w[k * p.D + a];
-  }
-  if (tid < F) s_obs[tid] = p.env_state[(long)n * F + tid];
 
-  // episode bookkeeping lives in thread 0's registers across the S steps
-  int steps = 0;
-  float run = 0.0f;
-  unsigned tick = p.tick[n];  // every thread tracks it (hash counter)
-  if (tid == 0) {
-    s_fir = p.is_fir[n];
-    steps = p.ep_steps[n];
-    run = p.ep_run[n];
-  }
-  __syncthreads();
-
-  for (int t = 0; t < p.S; ++t) {
-    const long row = (long)n * p.S + t;
-    tick += 1u;
-    // record the pre-step obs / hx / cx / is_fir; body GEMV + ReLU
+  // Record the pre-step obs / hx / cx / is_fir into output row ``row``, then
+  // body GEMV + ReLU, gates, cell update. Three barriers, the last one after
+  // the cell update: on return s_h / s_c hold the new recurrent state.
+  __device__ __forceinline__ void step(const RolloutArgs& p, int tid, long row,
+                                       const float* s_obs, const float* s_fir,
+                                       float* s_xb, float* s_h, float* s_c,
+                                       float* s_gates) {
     if (tid < F) p.obs[row * F + tid] = s_obs[tid];
-    if (tid == 0) p.is_fir_out[row] = s_fir;
+    if (tid == 0) p.is_fir_out[row] = *s_fir;
     if (tid < H) {
       p.hx[row * H + tid] = s_h[tid];
       p.cx[row * H + tid] = s_c[tid];
@@ -244,6 +264,59 @@ __global__ __launch_bounds__(4 * H) void rollout_discrete(RolloutArgs p) {
       s_h[tid] = s_gates[3 * H + tid] * tanhf(c_new);
     }
     __syncthreads();
+  }
+};
+
+template <int H, typename Env>
+__global__ __launch_bounds__(4 * H) void rollout_discrete(RolloutArgs p) {
+  constexpr int G = 4 * H;
+  constexpr int F = Env::kObsDim;
+  constexpr int A = Env::kActions;
+  const int tid = threadIdx.x;
+  const int n = blockIdx.x;
+  if (n >= p.N) return;  // uniform per workgroup
+
+  __shared__ __attribute__((aligned(16))) float s_xb[H];
+  __shared__ __attribute__((aligned(16))) float s_h[H];
+  __shared__ __attribute__((aligned(16))) float s_c[H];
+  __shared__ __attribute__((aligned(16))) float s_gates[G];
+  __shared__ float s_hw[A * H];  // logits head columns, [a][k]
+  __shared__ float s_obs[F];
+  __shared__ float s_cand[A * F];  // next state for every action
+  __shared__ float s_crew[A];
+  __shared__ int s_cterm[A];
+  __shared__ float s_ur[4];  // reset uniforms of this tick
+  __shared__ float s_fir;
+  __shared__ int s_reset;
+
+  RecurrentCore<H, F> core;
+  core.load(p, tid, n, s_h, s_c);
+  float hb[A];
+#pragma unroll
+  for (int a = 0; a < A; ++a) hb[a] = p.heads_b[a];
+
+  for (int idx = tid; idx < A * H; idx += G) {
+    const int a = idx / H, k = idx % H;
+    s_hw[idx] = p.heads_w[k * p.D + a];
+  }
+  if (tid < F) s_obs[tid] = p.env_state[(long)n * F + tid];
+
+  // episode bookkeeping lives in thread 0's registers across the S steps
+  int steps = 0;
+  float run = 0.0f;
+  unsigned tick = p.tick[n];  // every thread tracks it (hash counter)
+  if (tid == 0) {
+    s_fir = p.is_fir[n];
+    steps = p.ep_steps[n];
+    run = p.ep_run[n];
+  }
+  __syncthreads();
+
+  for (int t = 0; t < p.S; ++t) {
+    const long row = (long)n * p.S + t;
+    tick += 1u;
+    // record the pre-step obs / hx / cx / is_fir; body, gates, cell update
+    core.step(p, tid, row, s_obs, &s_fir, s_xb, s_h, s_c, s_gates);
 
     // logits = head columns [0, A): wave 0 splits the H-long dot products
     // over its lanes and butterfly-reduces them (a serial loop in one lane
@@ -361,6 +434,237 @@ __global__ __launch_bounds__(4 * H) void rollout_discrete(RolloutArgs p) {
   }
 }
 
+// ---- Gaussian policy (continuous control) ---------------------------------
+struct GaussianArgs : RolloutArgs {
+  float* ou_state;        // (N) persistent OU exploration state (Mode 1)
+  int ou_envs;            // envs [0, ou_envs) explore with OU noise forever
+  unsigned warmup_steps;  // every env explores while tick <= warmup_steps
+  float ou_theta, ou_sigma;
+};
+
+// Heads: column 0 = mu, column 1 = std (Mode 0, PPO-C) or log_std (Mode 1,
+// SAC-C); the ``logits`` field is [mu_raw | second_raw], ``act`` has width 1.
+// Per step, after the shared recurrent part: wave 0 butterfly-reduces the two
+// head columns while, in wave 1, one lane turns hash lanes 5 / 6 into the
+// step's standard normal (log / sqrt / cos), one evaluates the env's
+// action-independent drift and kResetDraws lanes draw the reset uniforms.
+// Thread 0 does the part of the scheme's transform that needs the heads only
+// before the barrier too, and after it the sample, the log-prob, the env
+// step, the bookkeeping and the reset. Five barriers a step, as in
+// rollout_discrete. The sampling chain uses the precise libm forms: parity
+// of the sample against the oracle is what the tests measure.
+template <int H, typename Env, int Mode>
+__global__ __launch_bounds__(4 * H) void rollout_gaussian(GaussianArgs p) {
+  // One tick has eight hash lanes: 1..4 reset, 5 / 6 the normal. A second
+  // action dimension needs a wider counter (rollout_rng.h).
+  static_assert(Env::kActDim == 1,
+                "eight hash lanes per tick allow exactly one action dimension");
+  static_assert(Env::kResetDraws >= 1 && Env::kResetDraws <= 4,
+                "reset draws use hash lanes 1..4");
+  static_assert(Mode == 0 || Mode == 1, "Mode: 0 = PPO-C, 1 = SAC-C");
+  constexpr int G = 4 * H;
+  constexpr int F = Env::kObsDim;
+  constexpr int R = Env::kResetDraws;
+  constexpr float kHalfLog2Pi = 0.9189385f;
+  const int tid = threadIdx.x;
+  const int n = blockIdx.x;
+  if (n >= p.N) return;  // uniform per workgroup
+
+  __shared__ __attribute__((aligned(16))) float s_xb[H];
+  __shared__ __attribute__((aligned(16))) float s_h[H];
+  __shared__ __attribute__((aligned(16))) float s_c[H];
+  __shared__ __attribute__((aligned(16))) float s_gates[G];
+  __shared__ float s_hw[2 * H];  // mu and std / log_std head columns, [a][k]
+  __shared__ float s_obs[F];
+  __shared__ float s_ur[R];  // reset uniforms of this tick
+  __shared__ float s_normal;
+  __shared__ float s_drift;
+  __shared__ float s_fir;
+  __shared__ int s_reset;
+
+  RecurrentCore<H, F> core;
+  core.load(p, tid, n, s_h, s_c);
+  float hb[2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a) hb[a] = p.heads_b[a];
+
+  for (int idx = tid; idx < 2 * H; idx += G) {
+    const int a = idx / H, k = idx % H;
+    s_hw[idx] = p.heads_w[k * p.D + a];
+  }
+  if (tid < F) s_obs[tid] = p.env_state[(long)n * F + tid];
+
+  // episode bookkeeping and the OU state live in thread 0's registers
+  int steps = 0;
+  float run = 0.0f, ou = 0.0f;
+  unsigned tick = p.tick[n];  // every thread tracks it (hash counter)
+  if (tid == 0) {
+    s_fir = p.is_fir[n];
+    steps = p.ep_steps[n];
+    run = p.ep_run[n];
+    if constexpr (Mode == 1) ou = p.ou_state[n];
+  }
+  __syncthreads();
+
+  for (int t = 0; t < p.S; ++t) {
+    const long row = (long)n * p.S + t;
+    tick += 1u;
+    core.step(p, tid, row, s_obs, &s_fir, s_xb, s_h, s_c, s_gates);
+
+    float lg[2];
+    if (tid < kWave) {
+      // the two head columns: wave 0 splits the H-long dot products over its
+      // lanes and butterfly-reduces them
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        float part = 0.0f;
+        for (int k = tid; k < H; k += kWave)
+          part = fmaf(s_h[k], s_hw[a * H + k], part);
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1)
+          part += __shfl_xor(part, off, kWave);
+        lg[a] = part + hb[a];
+      }
+    } else if (tid == kWave) {
+      // meanwhile, Box-Muller on hash lanes 5 (radius) and 6 (angle);
+      // 1 - u5 is exact in fp32 and never 0
+      const float u5 = pdrl_rng::uniform(p.seed, (unsigned)n, tick, 5u);
+      const float u6 = pdrl_rng::uniform(p.seed, (unsigned)n, tick, 6u);
+      s_normal = __fmul_rn(sqrtf(__fmul_rn(-2.0f, logf(1.0f - u5))),
+                           cosf(__fmul_rn(6.2831855f, u6)));
+    } else if (tid == kWave + 1) {
+      float st[F];
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+      s_drift = Env::drift(st);
+    } else if (tid < kWave + 2 + R) {
+      const unsigned k = (unsigned)(tid - kWave - 2);
+      s_ur[k] = pdrl_rng::uniform(p.seed, (unsigned)n, tick, k + 1u);
+    }
+    // The part of the transform that needs the heads only (thread 0, which
+    // holds them) goes before the barrier, under wave 1's chains. Mode 0,
+    // PPO-C: Normal(tanh(mu), softplus(std) + 1e-4), loc = mean and ls =
+    // log(sd); mode 1, SAC-C: tanh-squashed Normal(mu, exp(clamp(log_std))),
+    // loc = mu and ls the clamped log_std.
+    float loc = 0.0f, sd = 0.0f, ls = 0.0f;
+    if (tid == 0) {
+      p.logits[row * 2] = lg[0];
+      p.logits[row * 2 + 1] = lg[1];
+      if constexpr (Mode == 0) {
+        loc = tanhf(lg[0]);
+        sd = (lg[1] > 20.0f ? lg[1] : log1pf(expf(lg[1]))) + 1e-4f;
+        ls = logf(sd);
+      } else {
+        loc = lg[0];
+        ls = fminf(fmaxf(lg[1], -20.0f), 2.0f);
+        sd = expf(ls);
+      }
+    }
+    __syncthreads();
+
+    // sample, log-prob, env step, termination, auto-reset (thread 0)
+    if (tid == 0) {
+      const float nrm = s_normal;
+      float act, lp;
+      if constexpr (Mode == 0) {
+        // the action is stored unclipped, as the workers do
+        act = __fadd_rn(loc, __fmul_rn(sd, nrm));
+        lp = -0.5f * nrm * nrm - ls - kHalfLog2Pi;
+      } else {
+        const float mu = loc;
+        float z, quad;
+        if (n < p.ou_envs || tick <= p.warmup_steps) {
+          // OU exploration: correlated noise replaces the policy sample; the
+          // log-prob is the policy's density at that action
+          ou = __fadd_rn(__fsub_rn(ou, __fmul_rn(p.ou_theta, ou)),
+                         __fmul_rn(p.ou_sigma, nrm));
+          z = ou;
+          const float q = (z - mu) / sd;
+          quad = -0.5f * (q * q);
+        } else {
+          z = __fadd_rn(mu, __fmul_rn(sd, nrm));
+          quad = -0.5f * nrm * nrm;
+        }
+        act = tanhf(z);
+        // 1 - a*a + 1e-7 without fma contraction: with the same action it
+        // equals the oracle's value to the last bit, so the logf that
+        // amplifies it (by up to 2 / (1 - a*a)) sees no extra difference
+        const float om =
+            __fadd_rn(__fsub_rn(1.0f, __fmul_rn(act, act)), 1e-7f);
+        lp = quad - ls - kHalfLog2Pi - logf(om);
+      }
+      p.act[row] = act;
+      p.log_prob[row] = lp;
+
+      float st[F];
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+      float reward;
+      bool terminated;
+      Env::step(st, act, s_drift, reward, terminated);
+      steps += 1;
+      run += reward;
+      p.rew[row] = reward;
+      const bool done = terminated || steps >= p.max_episode_steps;
+      const bool reset = done || steps >= p.time_horizon;
+      p.ep_ret[row] = reset ? run : kNoEpisode;
+      if (reset) {
+        Env::reset(st, s_ur);
+        steps = 0;
+        run = 0.0f;
+        ou = 0.0f;
+      }
+#pragma unroll
+      for (int k = 0; k < F; ++k) s_obs[k] = st[k];
+      s_fir = reset ? 1.0f : 0.0f;
+      s_reset = reset ? 1 : 0;
+    }
+    __syncthreads();
+    // thread j is the only reader of s_h[j] / s_c[j] before the next barrier
+    if (s_reset != 0 && tid < H) {
+      s_h[tid] = 0.0f;
+      s_c[tid] = 0.0f;
+    }
+  }
+
+  // persist the per-env state for the next launch
+  if (tid < H) {
+    p.h[(long)n * H + tid] = s_h[tid];
+    p.c[(long)n * H + tid] = s_c[tid];
+  }
+  if (tid < F) p.env_state[(long)n * F + tid] = s_obs[tid];
+  if (tid == 0) {
+    p.is_fir[n] = s_fir;
+    p.ep_steps[n] = steps;
+    p.ep_run[n] = run;
+    p.tick[n] = tick;
+    if constexpr (Mode == 1) p.ou_state[n] = ou;
+  }
+}
+
+template <int H, typename Env>
+void launch_gaussian_mode(const GaussianArgs& a, int mode) {
+  const dim3 grid(a.N), block(4 * H);
+  if (mode == 0)
+    hipLaunchKernelGGL((rollout_gaussian<H, Env, 0>), grid, block, 0,
+                       current_stream(), a);
+  else
+    hipLaunchKernelGGL((rollout_gaussian<H, Env, 1>), grid, block, 0,
+                       current_stream(), a);
+}
+
+template <typename Env>
+void launch_gaussian(const GaussianArgs& a, int H, int mode) {
+  switch (H) {
+    case 32: launch_gaussian_mode<32, Env>(a, mode); break;
+    case 64: launch_gaussian_mode<64, Env>(a, mode); break;
+    case 128: launch_gaussian_mode<128, Env>(a, mode); break;
+    default:
+      TORCH_CHECK(false, "hidden size ", H, " unsupported (32/64/128)");
+  }
+  HIP_CHECK_LAST();
+}
+
 template <typename Env>
 void launch_env(const RolloutArgs& a, int H) {
   const dim3 grid(a.N);
@@ -397,10 +701,10 @@ void check_f32(const at::Tensor& t, long n, const char* name) {
               " elements");
 }
 
-}  // namespace
-
-// env_id: 0 = CartPole-v1 (ids are assigned in pdrl_amd/ops/rollout.py).
-void rollout_discrete_hip(
+// Argument checks and pointer packing shared by both entry points. The env
+// fixes obs_dim (F_env, else env_msg is raised) and A, the width of the
+// ``logits`` field and the number of leading head columns the kernel reads.
+RolloutArgs pack_rollout_args(
     const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
     const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
     const at::Tensor& heads_b, at::Tensor& env_state, at::Tensor& h,
@@ -408,8 +712,8 @@ void rollout_discrete_hip(
     at::Tensor& ep_run, at::Tensor& tick, at::Tensor& obs, at::Tensor& act,
     at::Tensor& rew, at::Tensor& logits, at::Tensor& log_prob,
     at::Tensor& is_fir_out, at::Tensor& hx, at::Tensor& cx,
-    at::Tensor& ep_ret, long env_id, long seed, long time_horizon,
-    long max_episode_steps) {
+    at::Tensor& ep_ret, long F_env, const char* env_msg, long A, long seed,
+    long time_horizon, long max_episode_steps) {
   CHECK_IN(body_w); CHECK_IN(body_b); CHECK_IN(w_ih); CHECK_IN(w_hh);
   CHECK_IN(b_g); CHECK_IN(heads_w); CHECK_IN(heads_b);
   TORCH_CHECK(body_w.dim() == 2 && w_ih.dim() == 2 && heads_w.dim() == 2 &&
@@ -417,15 +721,7 @@ void rollout_discrete_hip(
               "rollout: bad tensor ranks");
   const long F = body_w.size(0), H = body_w.size(1), D = heads_w.size(1);
   const long N = env_state.size(0), S = obs.size(1);
-  int A = 0;
-  switch (env_id) {
-    case 0:
-      TORCH_CHECK(F == CartPoleDyn::kObsDim, "CartPole needs obs_dim 4");
-      A = CartPoleDyn::kActions;
-      break;
-    default:
-      TORCH_CHECK(false, "rollout: unknown device env id ", env_id);
-  }
+  TORCH_CHECK(F == F_env, env_msg);
   TORCH_CHECK(N >= 1 && S >= 1, "rollout: empty batch");
   TORCH_CHECK(D >= A && heads_w.size(0) == H, "heads_w shape");
   check_f32(body_b, H, "body_b");
@@ -488,9 +784,92 @@ void rollout_discrete_hip(
   a.seed = (unsigned)seed;
   a.time_horizon = (int)std::min<long>(time_horizon, INT32_MAX);
   a.max_episode_steps = (int)std::min<long>(max_episode_steps, INT32_MAX);
+  return a;
+}
 
+}  // namespace
+
+// env_id: 0 = CartPole-v1 (ids are assigned in pdrl_amd/ops/rollout.py).
+void rollout_discrete_hip(
+    const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
+    const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
+    const at::Tensor& heads_b, at::Tensor& env_state, at::Tensor& h,
+    at::Tensor& c, at::Tensor& is_fir, at::Tensor& ep_steps,
+    at::Tensor& ep_run, at::Tensor& tick, at::Tensor& obs, at::Tensor& act,
+    at::Tensor& rew, at::Tensor& logits, at::Tensor& log_prob,
+    at::Tensor& is_fir_out, at::Tensor& hx, at::Tensor& cx,
+    at::Tensor& ep_ret, long env_id, long seed, long time_horizon,
+    long max_episode_steps) {
+  long F_env = 0, A = 0;
+  const char* env_msg = "";
   switch (env_id) {
-    case 0: launch_env<CartPoleDyn>(a, (int)H); break;
+    case 0:
+      F_env = CartPoleDyn::kObsDim;
+      A = CartPoleDyn::kActions;
+      env_msg = "CartPole needs obs_dim 4";
+      break;
+    default:
+      TORCH_CHECK(false, "rollout: unknown device env id ", env_id);
+  }
+  const RolloutArgs a = pack_rollout_args(
+      body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, env_state, h, c,
+      is_fir, ep_steps, ep_run, tick, obs, act, rew, logits, log_prob,
+      is_fir_out, hx, cx, ep_ret, F_env, env_msg, A, seed, time_horizon,
+      max_episode_steps);
+  switch (env_id) {
+    case 0: launch_env<CartPoleDyn>(a, (int)body_w.size(1)); break;
+  }
+}
+
+// Gaussian-policy sibling. env_id: 1 = MountainCarContinuous-v0. mode: 0 =
+// heads (mu, std), PPO-C sampling; 1 = heads (mu, log_std), SAC-C sampling
+// with optional OU exploration (ou_envs, warmup_steps; see GaussianArgs).
+void rollout_gaussian_hip(
+    const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
+    const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
+    const at::Tensor& heads_b, at::Tensor& env_state, at::Tensor& h,
+    at::Tensor& c, at::Tensor& is_fir, at::Tensor& ep_steps,
+    at::Tensor& ep_run, at::Tensor& tick, at::Tensor& ou_state,
+    at::Tensor& obs, at::Tensor& act, at::Tensor& rew, at::Tensor& logits,
+    at::Tensor& log_prob, at::Tensor& is_fir_out, at::Tensor& hx,
+    at::Tensor& cx, at::Tensor& ep_ret, long env_id, long mode, long seed,
+    long time_horizon, long max_episode_steps, long ou_envs,
+    long warmup_steps, double ou_theta, double ou_sigma) {
+  long F_env = 0;
+  const char* env_msg = "";
+  switch (env_id) {
+    case 1:
+      F_env = MountainCarContDyn::kObsDim;
+      env_msg = "MountainCarContinuous needs obs_dim 2";
+      break;
+    default:
+      TORCH_CHECK(false, "rollout: unknown continuous device env id ", env_id);
+  }
+  TORCH_CHECK(mode == 0 || mode == 1, "rollout: mode must be 0 or 1");
+  TORCH_CHECK(ou_envs >= 0 && warmup_steps >= 0,
+              "rollout: ou_envs and warmup_steps must not be negative");
+  TORCH_CHECK(mode == 1 || (ou_envs == 0 && warmup_steps == 0),
+              "rollout: OU exploration needs mode 1 (mu, log_std)");
+  // logits field = [mu | std or log_std]: two head columns
+  GaussianArgs a;
+  static_cast<RolloutArgs&>(a) = pack_rollout_args(
+      body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, env_state, h, c,
+      is_fir, ep_steps, ep_run, tick, obs, act, rew, logits, log_prob,
+      is_fir_out, hx, cx, ep_ret, F_env, env_msg, 2, seed, time_horizon,
+      max_episode_steps);
+  TORCH_CHECK(a.D >= 2, "heads_w shape");
+  check_f32(ou_state, a.N, "ou_state");
+  TORCH_CHECK(ou_state.device() == body_w.device(),
+              "rollout: tensors on different devices");
+  a.ou_state = ou_state.data_ptr<float>();
+  a.ou_envs = (int)std::min<long>(ou_envs, INT32_MAX);
+  a.warmup_steps = (unsigned)std::min<long>(warmup_steps, UINT32_MAX);
+  a.ou_theta = (float)ou_theta;
+  a.ou_sigma = (float)ou_sigma;
+  switch (env_id) {
+    case 1:
+      launch_gaussian<MountainCarContDyn>(a, (int)body_w.size(1), (int)mode);
+      break;
   }
 }
 

@@ -25,9 +25,13 @@ PDRL_HD uint32_t wang(uint32_t s) {
   return s;
 }
 
-// Lane k of env's draw at ``tick``: k = 0 is the action uniform, k = 1..4
-// the reset state of a reset caused by the step at ``tick`` (tick 0: the
-// initial state at construction). Result in [0, 1), a multiple of 2^-24.
+// Lane k of env's draw at ``tick`` (eight lanes per tick): k = 0 is the
+// categorical action uniform (unused by Gaussian policies), k = 1..4 the
+// reset state of a reset caused by the step at ``tick`` (tick 0: the initial
+// state at construction), k = 5 / 6 the radius / angle uniform of a Gaussian
+// policy's one standard normal per tick, k = 7 is free. One normal per tick
+// is one action dimension: more need a wider counter than tick * 8 + k.
+// Result in [0, 1), a multiple of 2^-24.
 PDRL_HD float uniform(uint32_t seed, uint32_t env, uint32_t tick, uint32_t k) {
   const uint32_t h0 = wang(seed ^ (env * 0x9E3779B1u));
   const uint32_t h = wang(h0 ^ wang(tick * 8u + k + 0x85ebca6bu));

@@ -1,13 +1,14 @@
 """Device actor: N native environments stepped by the policy on the GPU.
 
 ``DeviceRollout.rollout()`` advances ``num_envs`` environments by
-``seq_len`` steps — policy forward, categorical sample, log-prob, env
-dynamics, termination, auto-reset — and returns the ``(N, S, dim)`` batch in
-the learner's own field layout (``buffers.rollout_fields``). On a GPU this is
-ONE launch of the HIP kernel ``rollout_discrete`` (csrc/rollout.hip) reading
-the core's live weights by pointer; on a CPU device, or with
-``PDRL_ROLLOUT_EAGER=1``, the same class runs the pure-torch fp32 reference
-below, which is both the CPU fallback and the kernel's oracle.
+``seq_len`` steps — policy forward, sample, log-prob, env dynamics,
+termination, auto-reset — and returns the ``(N, S, dim)`` batch in the
+learner's own field layout (``buffers.rollout_fields``). On a GPU this is ONE
+launch of a HIP kernel of csrc/rollout.hip reading the core's live weights by
+pointer — ``rollout_discrete`` (categorical policy) or ``rollout_gaussian``
+(continuous control), chosen by the env's dynamics class; on a CPU device, or
+with ``PDRL_ROLLOUT_EAGER=1``, the same class runs the pure-torch fp32
+reference below, which is both the CPU fallback and the kernels' oracle.
 
 Random stream (shared with csrc/rollout_rng.h, all uint32):
 
@@ -16,9 +17,31 @@ Random stream (shared with csrc/rollout_rng.h, all uint32):
     h  = wang(h0 ^ wang(tick*8 + k + 0x85ebca6b))
     u(seed, env, tick, k) = float(h >> 8) * 2^-24        # in [0, 1)
 
-Lane k=0 is the action uniform of step ``tick`` (first step ever: tick 1);
-lanes 1..4 are the reset state of a reset caused by the step at ``tick``;
-the initial state at construction uses tick 0.
+Eight lanes per (env, tick). Lane k=0 is the categorical action uniform of
+step ``tick`` (first step ever: tick 1; unused by Gaussian policies); lanes
+1..4 are the reset state of a reset caused by the step at ``tick``; lanes 5
+and 6 are the radius and the angle of a Gaussian policy's one standard normal
+
+    n(seed, env, tick) = sqrt(-2 * log(1 - u5)) * cos(6.2831855 * u6)
+
+(``1 - u5`` is exact in fp32 and never 0); lane 7 is free. The initial state
+at construction uses tick 0. One normal per tick means one action dimension:
+more need a wider counter.
+
+Gaussian policies (heads ``mu`` then ``std`` | ``log_std``; the schemes of
+cpu_actor.cpp::act_batch_gaussian; ``logits`` is ``[mu_raw | second_raw]``):
+
+    mode 0 (PPO-C, std):   mean = tanh(mu); sd = softplus(s) + 1e-4
+                           act = mean + sd*n            (stored unclipped)
+                           lp  = -0.5*n*n - log(sd) - 0.9189385
+    mode 1 (SAC-C, log_std): ls = clamp(s, -20, 2); sd = exp(ls)
+                           z = mu + sd*n; act = tanh(z)
+                           lp  = -0.5*n*n - ls - 0.9189385 - log(1 - act² + 1e-7)
+    OU exploration (mode 1; env i at a step with i < ou_envs or
+    tick <= warmup_steps; ``ou_state`` is zeroed on every reset):
+                           ou = ou - theta*ou + sigma*n; z = ou; act = tanh(z)
+                           lp  = -0.5*((z-mu)/sd)² - ls - 0.9189385
+                                 - log(1 - act² + 1e-7)
 
 Env state is NOT checkpointed: a resumed run starts fresh episodes.
 """
@@ -105,7 +128,77 @@ class CartPoleDyn:
                              (state[:, 2].abs() - cls.THETA_THRESHOLD).abs())
 
 
-DEVICE_ENVS = {"CartPole-v1": CartPoleDyn}
+class MountainCarContDyn:
+    """MountainCarContinuous-v0: constants and update of
+    envs/mountain_car.py, fp32. A continuous-action env: ``act_dim`` instead
+    of ``n_actions``, ``step`` takes a float action, and the reset draws
+    hash lane 1 only."""
+
+    env_id = 1
+    obs_dim = 2
+    act_dim = 1
+    reset_draws = 1
+    max_episode_steps = 999
+    MIN_POSITION, MAX_POSITION, MAX_SPEED = -1.2, 0.6, 0.07
+    GOAL_POSITION, GOAL_VELOCITY, POWER = 0.45, 0.0, 0.0015
+
+    @staticmethod
+    def reset(u: torch.Tensor) -> torch.Tensor:
+        """u: (N, 1) uniforms → (pos in [-0.6, -0.4), vel 0)."""
+        pos = -0.6 + 0.2 * u[:, 0]
+        return torch.stack([pos, torch.zeros_like(pos)], 1)
+
+    @classmethod
+    def _advance(cls, state: torch.Tensor, action: torch.Tensor):
+        pos, vel = state.unbind(1)
+        force = action.clamp(-1.0, 1.0)
+        vel = (vel + (force * cls.POWER - 0.0025 * torch.cos(3 * pos))).clamp(
+            -cls.MAX_SPEED, cls.MAX_SPEED)
+        raw = pos + vel
+        pos = raw.clamp(cls.MIN_POSITION, cls.MAX_POSITION)
+        vel = torch.where((pos <= cls.MIN_POSITION) & (vel < 0),
+                          torch.zeros_like(vel), vel)
+        return force, raw, pos, vel
+
+    @classmethod
+    def step(cls, state: torch.Tensor, action: torch.Tensor):
+        """state (N,2) fp32, action (N,) fp32 → (state', reward, terminated)."""
+        force, _, pos, vel = cls._advance(state, action)
+        terminated = (pos >= cls.GOAL_POSITION) & (vel >= cls.GOAL_VELOCITY)
+        reward = -0.1 * force * force + torch.where(terminated, 100.0, 0.0).to(state.dtype)
+        return torch.stack([pos, vel], 1), reward, terminated
+
+    @classmethod
+    def threshold_margin(cls, state: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
+        """Smallest distance, over the step from PRE-step ``state`` under
+        ``action``, to a place where one float rounding changes the
+        trajectory discontinuously: the unclamped position from the left
+        wall (velocity zeroing), the position from the goal, and the
+        velocity from 0 once past the goal. The clamps are continuous."""
+        _, raw, pos, vel = cls._advance(state, action)
+        margin = torch.minimum((raw - cls.MIN_POSITION).abs(),
+                               (pos - cls.GOAL_POSITION).abs())
+        past_goal = pos >= cls.GOAL_POSITION
+        return torch.where(past_goal, torch.minimum(margin, vel.abs()), margin)
+
+
+DEVICE_ENVS = {"CartPole-v1": CartPoleDyn,
+               "MountainCarContinuous-v0": MountainCarContDyn}
+# head names[:2] → sampling scheme of a Gaussian policy (as the worker chooses)
+GAUSSIAN_MODES = {("mu", "std"): 0, ("mu", "log_std"): 1}
+HALF_LOG_2PI = 0.9189385
+
+
+def is_continuous_env(env_name: str) -> bool:
+    """True when the env has device dynamics with a continuous action."""
+    return hasattr(DEVICE_ENVS.get(env_name), "act_dim")
+
+
+def normal(seed: int, env: torch.Tensor, tick) -> torch.Tensor:
+    """The standard normal of (env, tick): Box-Muller on hash lanes 5 / 6."""
+    u5 = uniform(seed, env, tick, 5)
+    u6 = uniform(seed, env, tick, 6)
+    return torch.sqrt(-2.0 * torch.log(1.0 - u5)) * torch.cos(6.2831855 * u6)
 
 
 def has_device_env(env_name: str) -> bool:
@@ -120,26 +213,33 @@ class DeviceRollout:
 
     def __init__(self, core, env_name: str, num_envs: int, seq_len: int,
                  device, seed: int, time_horizon: int,
-                 max_episode_steps: int | None = None):
+                 max_episode_steps: int | None = None, *, ou_envs: int = 0,
+                 warmup_steps: int = 0, ou_theta: float = 0.15,
+                 ou_sigma: float = 0.6):
         if env_name not in DEVICE_ENVS:
             raise ValueError(
                 f"env {env_name!r} has no device dynamics "
                 f"(available: {sorted(DEVICE_ENVS)})")
         self.dyn = dyn = DEVICE_ENVS[env_name]
+        self.continuous = is_continuous_env(env_name)
         if getattr(core, "input2_dim", None) is not None:
             raise ValueError("DeviceRollout does not support dual-body cores")
-        if not core.head_names or core.head_names[0] != "logits":
+        if self.continuous:
+            self._check_gaussian_core(core, env_name)
+            self.mode = GAUSSIAN_MODES[tuple(core.head_names[:2])]
+        else:
+            self._check_discrete_core(core, env_name)
+            self.mode = None
+        self.ou_envs, self.warmup_steps = int(ou_envs), int(warmup_steps)
+        self.ou_theta, self.ou_sigma = float(ou_theta), float(ou_sigma)
+        if self.ou_envs < 0 or self.warmup_steps < 0:
+            raise ValueError("ou_envs and warmup_steps must not be negative")
+        if (self.ou_envs or self.warmup_steps) and self.mode != 1:
+            # importance ratios of on-policy algorithms assume the actions
+            # came from the recorded policy, which OU actions do not
             raise ValueError(
-                "DeviceRollout needs a discrete policy core whose first head "
-                f"is 'logits' (got heads {core.head_names})")
-        if core.hidden not in (32, 64, 128):
-            raise ValueError(
-                f"hidden size {core.hidden} unsupported (32/64/128)")
-        if core.input_dim != dyn.obs_dim or core.head_dims["logits"] != dyn.n_actions:
-            raise ValueError(
-                f"core shape (obs {core.input_dim}, actions "
-                f"{core.head_dims['logits']}) does not match {env_name} "
-                f"(obs {dyn.obs_dim}, actions {dyn.n_actions})")
+                "OU exploration needs an off-policy Gaussian core with heads "
+                f"['mu', 'log_std'] (got heads {core.head_names})")
         if num_envs < 1 or seq_len < 1:
             raise ValueError("num_envs and seq_len must be positive")
         self.core = core
@@ -160,14 +260,16 @@ class DeviceRollout:
 
         N, S, H, dev = self.N, self.S, self.H, self.device
         f32 = dict(dtype=torch.float32, device=dev)
-        self.fields = rollout_fields(dyn.obs_dim, dyn.n_actions, H, False)
+        if self.continuous:  # logits = [mu | std or log_std], act of width 1
+            self.fields = rollout_fields(dyn.obs_dim, dyn.act_dim, H, True)
+        else:
+            self.fields = rollout_fields(dyn.obs_dim, dyn.n_actions, H, False)
         # the batch: same tensor objects on every call (graph-capturable)
         self.batch = {k: torch.zeros(N, S, d, **f32) for k, d in self.fields.items()}
         # persistent per-env state
         self._env_ids = torch.arange(N, device=dev, dtype=torch.int64)
-        u0 = torch.stack([uniform(self.seed, self._env_ids, 0, k)
-                          for k in range(1, dyn.obs_dim + 1)], 1)
-        self.env_state = dyn.reset(u0).contiguous()
+        self.env_state = dyn.reset(self._reset_uniforms(0)).contiguous()
+        self.ou_state = torch.zeros(N, **f32)  # OU exploration (Gaussian mode 1)
         self.h = torch.zeros(N, H, **f32)
         self.c = torch.zeros(N, H, **f32)
         self.is_fir = torch.ones(N, **f32)
@@ -184,6 +286,48 @@ class DeviceRollout:
         self._last50: deque[float] = deque(maxlen=50)
 
     # ------------------------------------------------------------------ #
+    def _check_discrete_core(self, core, env_name: str):
+        dyn = self.dyn
+        if not core.head_names or core.head_names[0] != "logits":
+            raise ValueError(
+                "DeviceRollout needs a discrete policy core whose first head "
+                f"is 'logits' (got heads {core.head_names})")
+        if core.hidden not in (32, 64, 128):
+            raise ValueError(
+                f"hidden size {core.hidden} unsupported (32/64/128)")
+        if core.input_dim != dyn.obs_dim or core.head_dims["logits"] != dyn.n_actions:
+            raise ValueError(
+                f"core shape (obs {core.input_dim}, actions "
+                f"{core.head_dims['logits']}) does not match {env_name} "
+                f"(obs {dyn.obs_dim}, actions {dyn.n_actions})")
+
+    def _check_gaussian_core(self, core, env_name: str):
+        dyn = self.dyn
+        if tuple((core.head_names or [])[:2]) not in GAUSSIAN_MODES:
+            raise ValueError(
+                f"DeviceRollout on {env_name} needs a Gaussian policy core "
+                "whose first heads are ['mu', 'std'] or ['mu', 'log_std'] "
+                f"(got heads {core.head_names})")
+        if core.hidden not in (32, 64, 128):
+            raise ValueError(
+                f"hidden size {core.hidden} unsupported (32/64/128)")
+        second = core.head_names[1]
+        # the counter hash has eight lanes per tick, which is one normal:
+        # more action dimensions need a wider counter (csrc/rollout_rng.h)
+        if (core.input_dim != dyn.obs_dim or core.head_dims["mu"] != dyn.act_dim
+                or core.head_dims[second] != dyn.act_dim):
+            raise ValueError(
+                f"core shape (obs {core.input_dim}, action dims "
+                f"{core.head_dims['mu']}/{core.head_dims[second]}) does not "
+                f"match {env_name} (obs {dyn.obs_dim}, action dim "
+                f"{dyn.act_dim})")
+
+    def _reset_uniforms(self, tick) -> torch.Tensor:
+        """(N, draws) uniforms of a reset caused by ``tick``: lanes 1.."""
+        draws = getattr(self.dyn, "reset_draws", self.dyn.obs_dim)
+        return torch.stack([uniform(self.seed, self._env_ids, tick, k)
+                            for k in range(1, draws + 1)], 1)
+
     def _weights(self):
         c = self.core
         return (c.body_w, c.body_b, c.w_ih, c.w_hh, c.b_g, c.heads_w, c.heads_b)
@@ -195,7 +339,20 @@ class DeviceRollout:
         ep_ret = self._ep_ring[self._slot]
         self._slot += 1
         if self.eager:
-            self._rollout_eager(ep_ret)
+            if self.continuous:
+                self._rollout_eager_gaussian(ep_ret)
+            else:
+                self._rollout_eager(ep_ret)
+        elif self.continuous:
+            b = self.batch
+            self._ext.rollout_gaussian(
+                *(w.detach() for w in self._weights()),
+                self.env_state, self.h, self.c, self.is_fir, self.ep_steps,
+                self.ep_run, self.tick, self.ou_state, b["obs"], b["act"],
+                b["rew"], b["logits"], b["log_prob"], b["is_fir"], b["hx"],
+                b["cx"], ep_ret, self.dyn.env_id, self.mode, self.seed,
+                self.time_horizon, self.max_episode_steps, self.ou_envs,
+                min(self.warmup_steps, _M32), self.ou_theta, self.ou_sigma)
         else:
             b = self.batch
             self._ext.rollout_discrete(
@@ -206,6 +363,65 @@ class DeviceRollout:
                 ep_ret, self.dyn.env_id, self.seed, self.time_horizon,
                 self.max_episode_steps)
         return self.batch
+
+    def _rollout_eager_gaussian(self, ep_ret: torch.Tensor):
+        """fp32 torch reference of ``rollout_gaussian``: the formulas of the
+        module docstring on ``SeqLSTMCore._forward_eager``. Sampling a
+        Gaussian has no decision boundary, so ``margin`` records the env's
+        threshold distances only."""
+        dyn, b = self.dyn, self.batch
+        second = self.core.head_names[1]
+        for t in range(self.S):
+            self.tick += 1
+            b["obs"][:, t] = self.env_state
+            b["hx"][:, t] = self.h
+            b["cx"][:, t] = self.c
+            b["is_fir"][:, t, 0] = self.is_fir
+            outs, h, c = self.core._forward_eager(
+                self.env_state.unsqueeze(1), self.h, self.c)
+            mu, s = outs["mu"][:, 0, 0], outs[second][:, 0, 0]
+            n = normal(self.seed, self._env_ids, self.tick)
+            if self.mode == 0:
+                mean = torch.tanh(mu)
+                sd = torch.nn.functional.softplus(s) + 1e-4
+                act = mean + sd * n
+                log_prob = -0.5 * n * n - torch.log(sd) - HALF_LOG_2PI
+            else:
+                ls = s.clamp(-20.0, 2.0)
+                sd = torch.exp(ls)
+                tick = self.tick.to(torch.int64) & _M32
+                explore = (self._env_ids < self.ou_envs) | (tick <= self.warmup_steps)
+                ou = self.ou_state - self.ou_theta * self.ou_state + self.ou_sigma * n
+                self.ou_state = torch.where(explore, ou, self.ou_state)
+                z = torch.where(explore, ou, mu + sd * n)
+                q = (z - mu) / sd
+                quad = torch.where(explore, -0.5 * (q * q), -0.5 * n * n)
+                act = torch.tanh(z)
+                log_prob = (quad - ls - HALF_LOG_2PI
+                            - torch.log(1.0 - act * act + 1e-7))
+            self.margin = torch.minimum(
+                self.margin, dyn.threshold_margin(self.env_state, act))
+            state, rew, terminated = dyn.step(self.env_state, act)
+            self.ep_steps += 1
+            self.ep_run += rew
+            done = terminated | (self.ep_steps >= self.max_episode_steps)
+            reset = done | (self.ep_steps >= self.time_horizon)
+            b["act"][:, t, 0] = act
+            b["rew"][:, t, 0] = rew
+            b["logits"][:, t, 0] = mu
+            b["logits"][:, t, 1] = s
+            b["log_prob"][:, t, 0] = log_prob
+            ep_ret[:, t] = torch.where(reset, self.ep_run,
+                                       torch.full_like(rew, NO_EPISODE))
+            fresh = dyn.reset(self._reset_uniforms(self.tick))
+            keep = (~reset).to(torch.float32)
+            self.env_state = torch.where(reset[:, None], fresh, state)
+            self.h = h * keep[:, None]
+            self.c = c * keep[:, None]
+            self.ou_state = torch.where(reset, torch.zeros_like(keep), self.ou_state)
+            self.is_fir = reset.to(torch.float32)
+            self.ep_steps *= (~reset).to(torch.int32)
+            self.ep_run *= keep
 
     def _rollout_eager(self, ep_ret: torch.Tensor):
         """fp32 torch reference: same hash, op order of

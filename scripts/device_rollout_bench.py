@@ -6,7 +6,10 @@ synchronize, 50 warm-up calls, timed windows of at least ``--window`` s.
 (a) ``rollout()`` alone at N=128 and N=1024 (S=5, H=64);
 (b) rollout + IMPALA update in device mode at B=128 — the end-to-end figure
     to hold against ``bench.py --mode staged`` (the path this mode replaces)
-    and ``--mode resident`` (the ceiling: no data path at all).
+    and ``--mode resident`` (the ceiling: no data path at all);
+(c) the Gaussian ``rollout()`` alone on MountainCarContinuous-v0, both
+    sampling schemes (mode 0 = PPO-C, 1 = SAC-C), at N=128 and N=1024;
+(d) rollout + PPO-Continuous update in device mode at B=128.
 
 Prints one JSON line per measurement; ``values`` holds every repeat.
 """
@@ -58,8 +61,10 @@ def main():
     args = ap.parse_args()
 
     assert torch.cuda.is_available(), "needs a GPU"
-    from pdrl_amd.agents.learner_module import ImpalaUpdater
+    from pdrl_amd.agents.learner_module import ImpalaUpdater, PPOUpdater
     from pdrl_amd.networks import MlpLSTMSingle
+    from pdrl_amd.networks.models import (MlpLSTMSeperateContinuous,
+                                          MlpLSTMSingleContinuous)
     from pdrl_amd.ops.rollout import DeviceRollout
     from pdrl_amd.utils import load_params
 
@@ -96,6 +101,42 @@ def main():
             for _ in range(args.repeats)]
     games, mean50 = ro.episode_stats()
     report("device_mode_impala", vals, batch_size=p.batch_size, seq_len=S,
+           hidden=H, episodes=games, mean50=mean50)
+
+    # (c) Gaussian rollout alone, MountainCarContinuous-v0, both schemes
+    cenv = "MountainCarContinuous-v0"
+    for mode, cls in ((0, MlpLSTMSingleContinuous), (1, MlpLSTMSeperateContinuous)):
+        for n_envs in (128, 1024):
+            torch.manual_seed(0)
+            model = cls(2, 1, S, H).to(dev)
+            ro = DeviceRollout(model.actor.core, cenv, n_envs, S, dev, seed=1,
+                               time_horizon=500)
+            for _ in range(WARMUP):
+                ro.rollout()
+            vals = [timed(ro.rollout, args.window, n_envs * S, 200)
+                    for _ in range(args.repeats)]
+            report("rollout_only", vals, env=cenv, mode=mode, num_envs=n_envs,
+                   seq_len=S, hidden=H)
+
+    # (d) rollout + PPO-Continuous update, device mode, B=128
+    p = load_params()
+    p.algo, p.batch_size, p.seq_len, p.hidden_size = "PPO-Continuous", 128, S, H
+    p.env, p.obs_dim, p.n_actions, p.continuous = cenv, 2, 1, True
+    torch.manual_seed(1234)
+    model = MlpLSTMSingleContinuous(2, 1, S, H)
+    upd = PPOUpdater(model, p, dev)
+    ro = DeviceRollout(upd.model.actor.core, cenv, p.batch_size, S, dev,
+                       seed=1234, time_horizon=p.time_horizon)
+
+    def step_c():
+        upd.step(ro.rollout())
+
+    for _ in range(WARMUP):
+        step_c()
+    vals = [timed(step_c, args.window, p.batch_size * S, 200)
+            for _ in range(args.repeats)]
+    games, mean50 = ro.episode_stats()
+    report("device_mode_ppoc", vals, batch_size=p.batch_size, seq_len=S,
            hidden=H, episodes=games, mean50=mean50)
 
 
