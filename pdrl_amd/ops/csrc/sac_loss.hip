@@ -250,8 +250,8 @@ __global__ __launch_bounds__(4 * H) void sac_actor_bwd_kernel(
                       b, S, F, D, h0s, smem_raw);
 }
 
-// Actor wgrad + the actor-loss cross-row reduce: same grid as the generic
-// wgrad kernel plus ONE extra block (x == gridDim.x-1, y == 0) that sums
+// Actor wgrad + the actor-loss cross-row reduce: same flat grid as the
+// generic wgrad kernel plus ONE extra block (the last one) that sums
 // the (B,2) partials into {g_alpha, stats[0..3], alpha_norm} and advances
 // the shared Adam clock (saves the separate single-block loss kernel).
 template <int H>
@@ -270,7 +270,6 @@ __global__ __launch_bounds__(256) void sac_actor_wgrad_kernel(
     float beta2) {
   const int tid = threadIdx.x;
   if ((int)blockIdx.x == (int)gridDim.x - 1) {
-    if (blockIdx.y != 0) return;
     __shared__ float r0[256], r1[256];
     float l = 0.f, en = 0.f;
     for (int b = tid; b < B; b += 256) {
@@ -307,8 +306,8 @@ __global__ __launch_bounds__(256) void sac_actor_wgrad_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   wgrad_gates_body<H>(stash, h0, dgates, dw_ih, dw_hh, norm_sq, x, dxb, gouts,
                       dbody_w, dbody_b, db_g, dheads_w, dheads_b, F, D, N, S,
-                      h0s, smem_raw, blockIdx.x, blockIdx.y, nullptr, 0,
-                      nullptr, nullptr, H);
+                      h0s, smem_raw, blockIdx.x, nullptr, 0, nullptr, nullptr,
+                      H);
 }
 
 // Post-update actor forward + critic loss in ONE launch (the fwd+loss
@@ -478,10 +477,8 @@ void sac_actor_wgrad_hip(
   const int N = B * S;
   TORCH_CHECK(H == 64, "sac_actor_wgrad specialized for H=64");
   constexpr int G = 256;
-  const int gemm_blocks = (64 / 16) * (G / kWave);
   const int total_waves = F * 64 + 64 + G + 64 * D + D;
-  const int small_blocks = (total_waves * kWave + 255) / 256;
-  dim3 grid(gemm_blocks + small_blocks + 1, 2);
+  dim3 grid(wgrad_flat_grid<64>(total_waves) + 1);
   const int tab_lds = N * sizeof(const float*);
   TORCH_CHECK(tab_lds <= 64 * 1024, "wgrad row table exceeds LDS");
   hipLaunchKernelGGL(

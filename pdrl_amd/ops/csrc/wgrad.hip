@@ -34,8 +34,8 @@ __global__ __launch_bounds__(256) void wgrad_gates_mfma_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   wgrad_gates_body<H>(stash, h0, dgates, dw_ih, dw_hh, norm_sq, x, dxb, gouts,
                       dbody_w, dbody_b, db_g, dheads_w, dheads_b, F, D, N, S,
-                      h0s, smem_raw, blockIdx.x, blockIdx.y, x2, F2, dbody2_w,
-                      dbody2_b, half);
+                      h0s, smem_raw, blockIdx.x, x2, F2, dbody2_w, dbody2_b,
+                      half);
 }
 
 // Multi-core weight grads: blockIdx.z picks the network; per-core pointers
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void wgrad_gates_mfma_multi_kernel(
       reinterpret_cast<float*>(ct[6]), reinterpret_cast<float*>(ct[7]),
       reinterpret_cast<float*>(ct[8]), reinterpret_cast<float*>(ct[9]),
       reinterpret_cast<float*>(ct[10]), F, D, N, S, h0s, smem_raw,
-      blockIdx.x, blockIdx.y, x2, x2 != nullptr ? F2 : 0,
+      blockIdx.x, x2, x2 != nullptr ? F2 : 0,
       reinterpret_cast<float*>(ct[12]),
       reinterpret_cast<float*>(ct[13]), x2 != nullptr ? half : H);
 }
@@ -81,11 +81,10 @@ void launch_wgrad(const at::Tensor& x, const at::Tensor& h0,
   const int half = dual ? (int)dbody_w.size(1) : H;
   const int half2 = dual ? H - half : 0;
   const int F2 = dual ? (int)x2->size(-1) : 0;
-  // one fused launch: gate GEMM tiles + small-grad blocks side by side
-  const int gemm_blocks = (H / 16) * (G / kWave);
+  // one fused launch, flat grid: gate GEMM tiles (both GEMMs) first, then
+  // the small-grad blocks
   const int total_waves = F * half + half + F2 * half2 + half2 + G + H * D + D;
-  const int small_blocks = (total_waves * kWave + 255) / 256;
-  dim3 grid(gemm_blocks + small_blocks, 2);
+  dim3 grid(wgrad_flat_grid<H>(total_waves));
   const int tab_lds = N * sizeof(const float*);
   TORCH_CHECK(tab_lds <= 64 * 1024, "wgrad row table exceeds LDS (B*S too big)");
   float* nrm = norm_sq.has_value() ? norm_sq->data_ptr<float>() : nullptr;
@@ -127,11 +126,9 @@ void seq_lstm_wgrad_multi_hip(const at::Tensor& x, const at::Tensor& h0,
 #define PDRL_LAUNCH_WG_MULTI(HH)                                              \
   do {                                                                        \
     constexpr int G = 4 * HH;                                                 \
-    const int gemm_blocks = (HH / 16) * (G / kWave);                          \
     const int total_waves = F * halfv + halfv + F2v * half2 + half2 + G +     \
                             HH * (int)D + (int)D;                             \
-    const int small_blocks = (total_waves * kWave + 255) / 256;               \
-    dim3 grid(gemm_blocks + small_blocks, 2, (unsigned)C);                    \
+    dim3 grid(wgrad_flat_grid<HH>(total_waves), 1, (unsigned)C);              \
     hipLaunchKernelGGL((wgrad_gates_mfma_multi_kernel<HH>), grid, dim3(256),  \
                        tab_lds, current_stream(), x.data_ptr<float>(),        \
                        h0.data_ptr<float>(), x2p, tab.data_ptr<long>(), F,    \

@@ -8,6 +8,14 @@
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
+// A pointer read back from the LDS row table has lost its address space, and
+// a load through it is a flat load: those return out of order, so the
+// compiler waits for ALL outstanding memory operations (vmcnt(0)) at the
+// first use and no prefetch survives. The rows are always global memory
+// (stash or h0); saying so turns the loads into global loads with counted
+// in-order waits.
+using gptr_f32 = const __attribute__((address_space(1))) float*;
+
 // A-operand row n of the gate GEMMs: xb (sel 0) or hprev (sel 1).
 template <int H>
 __device__ __forceinline__ const float* gate_a_row(const float* stash,
@@ -23,8 +31,28 @@ __device__ __forceinline__ const float* gate_a_row(const float* stash,
   return stash + (long)(n - 1) * kStashFields * H + 6 * H;  // h field
 }
 
-// One wave computes one 16x16 tile of C = A^T · B.
-// blockIdx.x → (m0, g_base); 4 waves fan out over g; blockIdx.y → which GEMM.
+// Flat 1-D block index → the (bx, by) pair the tile mapping below is written
+// in: [0, 2·gemm_blocks) are the GEMM tiles of sel 0 then sel 1, everything
+// after that is a small-grad block (by == 0). No block is dispatched idle.
+template <int H>
+__device__ __forceinline__ void wgrad_flat_block(int bid, int& bx, int& by) {
+  constexpr int gemm_blocks = (H / 16) * (4 * H / kWave);
+  if (bid < 2 * gemm_blocks) {
+    by = bid / gemm_blocks;
+    bx = bid % gemm_blocks;
+  } else {
+    by = 0;
+    bx = bid - gemm_blocks;
+  }
+}
+
+// Host side of the same mapping: blocks in the flat wgrad grid.
+template <int H>
+inline int wgrad_flat_grid(int total_small_waves) {
+  constexpr int gemm_blocks = (H / 16) * (4 * H / kWave);
+  return 2 * gemm_blocks + (total_small_waves * kWave + 255) / 256;
+}
+
 template <int H>
 __device__ void wgrad_small_body(const float*, const float*, const float*,
                                  const float*, const float*, float*, float*,
@@ -32,9 +60,107 @@ __device__ void wgrad_small_body(const float*, const float*, const float*,
                                  int, int, const float*, int, float*, float*,
                                  int);
 
-// One launch covers BOTH gate-GEMMs (MFMA tiles) and the small grads:
-// blocks [0, gemm_blocks) × y∈{0,1} run the two GEMMs; blocks beyond that on
-// y==0 run the wave-per-element small-grad reductions concurrently.
+// K sweep of one wave's 16x16 tile over the nchunks full chunks of 4·U rows:
+// acc += A[n][m0+i] · B[n][g0+i] for n = 0 .. nchunks·4U-1, in that order on
+// ONE accumulator chain (the sum is bit-identical to a plain n loop).
+//
+// A ring of P chunks keeps P-1 chunks of loads in flight: chunk c's MFMA
+// chain runs behind the loads of chunk c+P-1. For that the waits must be
+// COUNTED (vmcnt(N) for the oldest chunk only), which needs three things:
+//  - global loads (gptr_f32 above): one flat load anywhere in the ring
+//    makes every wait a vmcnt(0) and the pipeline collapses to load→wait;
+//  - static slots: the loop is unrolled over P (runtime-indexed register
+//    arrays would go to scratch);
+//  - a steady-state loop with no branch around a load and a single exit, so
+//    the counts the compiler derives at its head are the steady-state ones.
+//    Chunks whose prefetch would run past K are peeled into a straight-line
+//    drain after the loop instead.
+// The row-pointer table is read one chunk ahead of its loads, so the LDS
+// round trip sits under the previous chunk's MFMAs as well.
+//
+// Depth: a wave's vmcnt counter is 6 bits (63 operations outstanding at
+// most) and a chunk is 2·U = 16 of them, so P <= 4. Measured at B·S = 640,
+// once the waits are counted one chunk of look-ahead covers most of the
+// latency: P = 3 beats P = 2 by 0.3 µs per step and P = 4 is slower again
+// (profiles/wgrad_latency.md).
+constexpr int kWgU = 8;  // MFMAs per chunk, 32 n-rows
+constexpr int kWgP = 3;  // ring depth in chunks (2·U·P = 48 operand VGPRs)
+static_assert(kWgP >= 2 && (kWgP - 1) * 2 * kWgU <= 63,
+              "the awaited chunk must be reachable by a counted vmcnt wait");
+
+template <int G>
+__device__ __forceinline__ f32x4 wgrad_sweep(const float* const* tab,
+                                             const float* __restrict__ dgates,
+                                             int nchunks, int acol, int bcol,
+                                             int k) {
+  constexpr int U = kWgU, P = kWgP, step = 4 * U;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (nchunks <= 0) return acc;
+  const int last = nchunks - 1;
+  float a[P][U], b[P][U];
+  gptr_f32 ap[U];  // A-row pointers of the NEXT chunk to load
+
+  // `chunk` is clamped to the last one wherever it can run past the end:
+  // the ring fill of a short sweep and the pointer read-ahead (a cache hit,
+  // never consumed).
+#define PDRL_WG_PTRS(chunk)                                                \
+  _Pragma("unroll") for (int u = 0; u < U; ++u) {                          \
+    ap[u] = (gptr_f32)tab[min((chunk), last) * step + 4 * u + k];          \
+  }
+#define PDRL_WG_LOAD(slot, chunk)                                          \
+  _Pragma("unroll") for (int u = 0; u < U; ++u) {                          \
+    const int n = min((chunk), last) * step + 4 * u + k;                   \
+    a[slot][u] = ap[u][acol];                                              \
+    b[slot][u] = dgates[(long)n * G + bcol];                               \
+  }
+#define PDRL_WG_MFMA(slot)                                                 \
+  __builtin_amdgcn_sched_barrier(0); /* keep loads issued ahead */         \
+  _Pragma("unroll") for (int u = 0; u < U; ++u) {                          \
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[slot][u], b[slot][u],     \
+                                               acc, 0, 0, 0);              \
+  }                                                                        \
+  __builtin_amdgcn_sched_barrier(0);
+
+  PDRL_WG_PTRS(0);
+#pragma unroll
+  for (int p = 0; p < P - 1; ++p) {  // fill the ring: chunks 0 .. P-2
+    PDRL_WG_LOAD(p, p);
+    PDRL_WG_PTRS(p + 1);
+  }
+  // Whole turns whose prefetches all lie inside K. Chunk c0+p sits in slot
+  // p; its turn issues chunk c0+p+P-1 into the slot chunk c0+p-1 just left.
+  int c0 = 0;
+  for (; c0 + 2 * P - 1 <= nchunks; c0 += P) {
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+      PDRL_WG_LOAD((p + P - 1) % P, c0 + p + P - 1);
+      PDRL_WG_PTRS(c0 + p + P);
+      PDRL_WG_MFMA(p);
+    }
+  }
+  // Drain: at most 2P-2 chunks left, straight-line on the same static
+  // slots; a chunk prefetches only while that stays inside K.
+#pragma unroll
+  for (int p = 0; p < 2 * P - 2; ++p) {
+    if (c0 + p >= nchunks) break;
+    if (c0 + p + P - 1 < nchunks) {
+      PDRL_WG_LOAD((p + P - 1) % P, c0 + p + P - 1);
+      PDRL_WG_PTRS(c0 + p + P);
+    }
+    PDRL_WG_MFMA(p % P);
+  }
+  return acc;
+#undef PDRL_WG_MFMA
+#undef PDRL_WG_PTRS
+#undef PDRL_WG_LOAD
+}
+
+// One wave computes one 16x16 tile of C = A^T · B.
+// bx → (m0, g_base); 4 waves fan out over g; by → which GEMM.
+//
+// One launch covers BOTH gate-GEMMs (MFMA tiles) and the small grads: the
+// flat block index (wgrad_flat_block) puts the 2·gemm_blocks GEMM blocks
+// first and the wave-per-element small-grad blocks after them.
 template <int H>
 __device__ __forceinline__ void wgrad_gates_body(
     const float* __restrict__ stash,   // (B,S,7H)
@@ -49,15 +175,16 @@ __device__ __forceinline__ void wgrad_gates_body(
     float* __restrict__ dbody_w, float* __restrict__ dbody_b,
     float* __restrict__ db_g, float* __restrict__ dheads_w,
     float* __restrict__ dheads_b, int F, int D,
-    int N, int S, long h0s, char* smem_raw, int bx, int by,
+    int N, int S, long h0s, char* smem_raw, int bid,
     const float* __restrict__ x2 = nullptr,  // (N,F2) dual-body second input
     int F2 = 0, float* __restrict__ dbody2_w = nullptr,
     float* __restrict__ dbody2_b = nullptr, int half = H) {
   constexpr int G = 4 * H;
   const int g_blocks = G / kWave;  // 64-wide g blocks
   const int gemm_blocks = (H / 16) * g_blocks;
+  int bx, by;
+  wgrad_flat_block<H>(bid, bx, by);
   if (bx >= gemm_blocks) {
-    if (by != 0) return;
     wgrad_small_body<H>(x, dxb, stash, dgates, gouts, dbody_w, dbody_b, db_g,
                         dheads_w, dheads_b, norm_sq, N, F, D,
                         (bx - gemm_blocks) * (256 / kWave),
@@ -83,54 +210,11 @@ __device__ __forceinline__ void wgrad_gates_body(
   }
   __syncthreads();
 
-  // Double-buffered software pipeline: the next chunk's 2×U loads issue
-  // BEFORE the current chunk's MFMA chain, so L2 latency hides under the
-  // matrix work (naive load→mfma loop: 61 µs on this shape).
-  constexpr int U = 8;  // MFMAs per chunk, 32 n-rows
-  const int step = 4 * U;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  float a0[U], b0[U], a1[U], b1[U];
-
-#define PDRL_WG_LOAD(av, bv, base)                                         \
-  _Pragma("unroll") for (int u = 0; u < U; ++u) {                          \
-    const int n = (base) + 4 * u + k;                                      \
-    av[u] = tab[n][m0 + i];                                                \
-    bv[u] = dgates[(long)n * G + g0 + i];                                  \
-  }
-#define PDRL_WG_MFMA(av, bv)                                               \
-  _Pragma("unroll") for (int u = 0; u < U; ++u) {                          \
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u], bv[u], acc, 0, 0, 0);\
-  }
-
-  const int nfull = N - (N % step);
-  int n0 = 0;
-  if (nfull >= step) {
-    PDRL_WG_LOAD(a0, b0, 0);
-    bool cur0 = true;
-    for (n0 = step; n0 < nfull; n0 += step) {
-      if (cur0) {
-        PDRL_WG_LOAD(a1, b1, n0);
-        __builtin_amdgcn_sched_barrier(0);  // keep loads issued ahead
-        PDRL_WG_MFMA(a0, b0);
-      } else {
-        PDRL_WG_LOAD(a0, b0, n0);
-        __builtin_amdgcn_sched_barrier(0);
-        PDRL_WG_MFMA(a1, b1);
-      }
-      cur0 = !cur0;
-    }
-    if (cur0) {
-      PDRL_WG_MFMA(a0, b0);
-    } else {
-      PDRL_WG_MFMA(a1, b1);
-    }
-    n0 = nfull;
-  }
-#undef PDRL_WG_LOAD
-#undef PDRL_WG_MFMA
-  for (; n0 < N; n0 += 4) {  // ragged tail, zero-padded
+  const int step = 4 * kWgU;
+  f32x4 acc = wgrad_sweep<G>(tab, dgates, N / step, m0 + i, g0 + i, k);
+  for (int n0 = N - (N % step); n0 < N; n0 += 4) {  // ragged tail, zero-padded
     const bool live = (n0 + k) < N;
-    const float a = live ? tab[n0 + k][m0 + i] : 0.f;
+    const float a = live ? ((gptr_f32)tab[n0 + k])[m0 + i] : 0.f;
     const float b = live ? dgates[(long)(n0 + k) * G + g0 + i] : 0.f;
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
   }
@@ -156,6 +240,8 @@ __device__ __forceinline__ void wgrad_gates_body(
   }
 }
 
+
+constexpr int kWgSmallUnroll = 4;  // rows in flight per lane, small grads
 
 // One wave per output element; lanes stride the K=N reduction.
 // Segments: dbody_w (F*half) | dbody_b (half) | dbody2_w (F2*half2) |
@@ -222,7 +308,24 @@ __device__ void wgrad_small_body(
 
   float acc = 0.f;
   if (live_wave) {
-    for (int n = lane; n < N; n += kWave) {
+    // R rounds of loads issue before the first dependent fmaf (one exposed
+    // round trip per R rows instead of one per row); the lane's accumulation
+    // order n = lane, lane+64, ... is unchanged.
+    constexpr int R = kWgSmallUnroll;
+    int n = lane;
+    for (; n + (R - 1) * kWave < N; n += R * kWave) {
+      float av[R], bv[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const long nr = n + r * kWave;
+        bv[r] = pb[nr * stride_b];
+        av[r] = (pa != nullptr) ? pa[nr * stride_a] : 0.f;
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+        acc = (pa != nullptr) ? fmaf(av[r], bv[r], acc) : acc + bv[r];
+    }
+    for (; n < N; n += kWave) {
       const float bv = pb[(long)n * stride_b];
       acc = (pa != nullptr) ? fmaf(pa[(long)n * stride_a], bv, acc) : acc + bv;
     }

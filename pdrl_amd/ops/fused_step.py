@@ -6,7 +6,7 @@ The loss math has ONE implementation — the row-local device functions of
 csrc/loss_row.h (plus V-MPO's cross-row vmpo_mid) — reached by two launch
 sequences:
 
-Fused rows (H=64, the default; 47 µs/step, profiles/algo_breakdown_r02c.md):
+Fused rows (H=64, the default; 41 µs/step, profiles/wgrad_latency.md):
   1. seq_lstm_fwd_loss  — forward + the row's loss phase (V-trace/GAE scans,
                           analytic head grads, per-row stat partials; for
                           V-MPO, the log-softmax + GAE pre-phase)
