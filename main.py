@@ -18,6 +18,8 @@ CLI (identical shape to the reference):
   python main.py learner_sub_process <learner_ip> <learner_port>
   python main.py manager_sub_process <manager_ip> <learner_ip> <port> <learner_port>
   python main.py worker_sub_process <num_p> <manager_ip> <learner_ip> <port> <learner_port>
+and, beyond the reference, the greedy return of a checkpoint:
+  python main.py evaluate [checkpoint]
 """
 from __future__ import annotations
 
@@ -328,6 +330,41 @@ def worker_sub_process(num_p, manager_ip, learner_ip, port, learner_port, *_):
                    params, hb, stop_event),
                   heartbeat=hb)
     sup.monitor()
+
+
+@register
+def evaluate(checkpoint=None, *_):
+    """Greedy return of a checkpoint (default: the newest one in
+    ``model_dir``): ``eval_envs`` x ``eval_episodes`` whole episodes of the
+    deterministic policy on the ``eval_seed`` start states, one launch on the
+    GPU when there is one, the eager reference otherwise. Prints one JSON
+    line."""
+    import json
+
+    from pdrl_amd.agents import find_latest_checkpoint
+    from pdrl_amd.ops.evaluate import DeviceEvaluator
+
+    params = probe_env_spaces(Params)
+    path = checkpoint or find_latest_checkpoint(params.model_dir, params.algo)
+    if path is None:
+        raise FileNotFoundError(
+            f"no {params.algo}_*.pt checkpoint in {params.model_dir!r}; "
+            f"pass one: python main.py evaluate <checkpoint>")
+    model = build_model(params)
+    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    model.load_state_dict(ckpt["modules"]["model"])
+    device = torch.device(
+        f"cuda:{select_least_used_gpu()}" if torch.cuda.is_available() else "cpu")
+    model = model.to(device).eval()
+    ev = DeviceEvaluator(
+        model.actor.core, params.env, int(getattr(params, "eval_envs", 64)),
+        int(getattr(params, "eval_episodes", 1)), device,
+        seed=int(getattr(params, "eval_seed", 4321)))
+    ev.evaluate()
+    print(json.dumps({
+        "algo": params.algo, "env": params.env, "checkpoint": str(path),
+        "envs": ev.N, "episodes": ev.E, **ev.summary(),
+    }), flush=True)
 
 
 # --------------------------------------------------------------------------- #

@@ -19,7 +19,11 @@ MI355X-first differences:
   dynamics (CartPole-v1 with a discrete policy, MountainCarContinuous-v0
   with a Gaussian one) the learner rolls out on the GPU itself
   (ops/rollout.py) and needs no ring, storage, manager or workers — see
-  ``Learner._init_device_actor``. Env state is not checkpointed.
+  ``Learner._init_device_actor``. Env state is not checkpointed;
+* greedy evaluation (``"eval_interval": N``, either actor mode): every N
+  updates rank 0 runs whole episodes of the deterministic policy on fixed
+  start states in one launch (ops/evaluate.py) and logs ``eval-mean-return``
+  — see ``Learner._init_evaluator``.
 """
 from __future__ import annotations
 
@@ -266,6 +270,11 @@ class Learner:
 
         self.on_policy = is_on_policy(params.algo)
         self.device_rollout = None
+        self.evaluator = None
+        self.last_eval = None
+        self.eval_interval = int(getattr(params, "eval_interval", 0) or 0)
+        if self.eval_interval > 0 and rank == 0:
+            self._init_evaluator()
         if getattr(params, "actor_mode", "workers") == "device":
             self._init_device_actor()
             return
@@ -300,6 +309,54 @@ class Learner:
         self.writer = SummaryWriter(params.result_dir) if self.is_root else None
         self.timer = ExecutionTimer(num_transition=params.seq_len * params.batch_size * world_size)
         self._replay_ready = False  # latching (reference: learner.py:385)
+
+    def _actor_core(self):
+        mods = self.updater.trainable_modules()
+        m = mods.get("model") or next(iter(mods.values()))
+        return getattr(m, "actor", m).core
+
+    def _init_evaluator(self):
+        """Greedy evaluation (``eval_interval > 0``, rank 0, either actor
+        mode): a ``DeviceEvaluator`` on the updater's actor core measures
+        the deterministic policy every ``eval_interval`` updates, always on
+        the same ``eval_envs`` x ``eval_episodes`` start states
+        (``eval_seed``). It has no state of its own and shares none with the
+        training rollout, the replay or ``shared_stat``."""
+        from pdrl_amd.ops.evaluate import DeviceEvaluator
+        from pdrl_amd.ops.rollout import has_device_env, is_continuous_env
+
+        p = self.params
+        continuous_algo = (p.algo.endswith("Continuous")
+                           or bool(getattr(p, "continuous", False)))
+        if not has_device_env(p.env):
+            raise ValueError(
+                f"eval_interval > 0: env {p.env!r} has no device dynamics to "
+                f"evaluate on; set eval_interval to 0")
+        if continuous_algo != is_continuous_env(p.env):
+            kind = "continuous" if is_continuous_env(p.env) else "discrete"
+            raise ValueError(
+                f"eval_interval > 0: device env {p.env!r} evaluates {kind} "
+                f"policies only (algo {p.algo!r} is "
+                f"{'continuous' if continuous_algo else 'discrete'})")
+        self.evaluator = DeviceEvaluator(
+            self._actor_core(), p.env, int(getattr(p, "eval_envs", 64)),
+            int(getattr(p, "eval_episodes", 1)), self.device,
+            seed=int(getattr(p, "eval_seed", 4321)))
+
+    def maybe_evaluate(self):
+        """Evaluate every ``eval_interval`` updates; log through the writer
+        and keep the summary in ``last_eval``."""
+        if self.evaluator is None:
+            return
+        n = self.updater.update_count
+        if n == 0 or n % self.eval_interval != 0:
+            return
+        self.evaluator.evaluate()
+        self.last_eval = dict(self.evaluator.summary(), update=n)
+        if self.writer is not None:
+            self.writer.add_scalar("eval-mean-return", self.last_eval["mean_return"], n)
+            self.writer.add_scalar("eval-min-return", self.last_eval["min_return"], n)
+            self.writer.add_scalar("eval-mean-length", self.last_eval["mean_length"], n)
 
     def _init_device_actor(self):
         """Device actor mode (``actor_mode == "device"``): the rollout never
@@ -486,6 +543,7 @@ class Learner:
             self.publish_model()
             self.log_stats(stats)
             self.save_checkpoint()
+            self.maybe_evaluate()
             if self.heartbeat is not None:
                 self.heartbeat.value = time.time()
             if max_updates is not None and self.updater.update_count >= max_updates:

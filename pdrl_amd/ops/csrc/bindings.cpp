@@ -48,6 +48,14 @@ void rollout_gaussian_hip(
     at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
     at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
     at::Tensor&, long, long, long, long, long, long, long, double, double);
+void rollout_eval_discrete_hip(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, at::Tensor&,
+    at::Tensor&, const c10::optional<at::Tensor>&, long, long, long);
+void rollout_eval_gaussian_hip(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, at::Tensor&,
+    at::Tensor&, const c10::optional<at::Tensor>&, long, long, long);
 double rollout_uniform_host(long, long, long, long);
 void seq_lstm_fwd_loss_hip(
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
@@ -263,6 +271,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mode"), py::arg("seed"), py::arg("time_horizon"),
         py::arg("max_episode_steps"), py::arg("ou_envs"),
         py::arg("warmup_steps"), py::arg("ou_theta"), py::arg("ou_sigma"));
+  m.def("rollout_eval_discrete", &rollout_eval_discrete_hip,
+        "greedy evaluation: E whole episodes per env under the arg-max "
+        "action in one launch; writes ep_ret / ep_len (N, E) only",
+        py::arg("body_w"), py::arg("body_b"), py::arg("w_ih"), py::arg("w_hh"),
+        py::arg("b_g"), py::arg("heads_w"), py::arg("heads_b"),
+        py::arg("ep_ret"), py::arg("ep_len"), py::arg("start_state"),
+        py::arg("env_id"), py::arg("seed"), py::arg("max_episode_steps"));
+  m.def("rollout_eval_gaussian", &rollout_eval_gaussian_hip,
+        "greedy evaluation for continuous control: rollout_eval_discrete's "
+        "contract with the action tanh(mu)",
+        py::arg("body_w"), py::arg("body_b"), py::arg("w_ih"), py::arg("w_hh"),
+        py::arg("b_g"), py::arg("heads_w"), py::arg("heads_b"),
+        py::arg("ep_ret"), py::arg("ep_len"), py::arg("start_state"),
+        py::arg("env_id"), py::arg("seed"), py::arg("max_episode_steps"));
   m.def("rollout_uniform", &rollout_uniform_host,
         "host evaluation of the rollout's counter-hash uniform",
         py::arg("seed"), py::arg("env"), py::arg("tick"), py::arg("k"));

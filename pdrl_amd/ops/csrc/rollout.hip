@@ -8,7 +8,8 @@
 // the eager oracle is pdrl_amd/ops/rollout.py. rollout_gaussian (below) is the
 // continuous-control sibling: same geometry and recurrent part, a Gaussian
 // policy (PPO-C / SAC-C sampling schemes of cpu_actor.cpp::act_batch_gaussian)
-// and a float action.
+// and a float action. rollout_eval_discrete / rollout_eval_gaussian (further
+// below) are the greedy evaluation kernels: whole episodes, no batch.
 //
 // Geometry: as seq_lstm_fwd_row (core_rows.h) — one 4H-thread workgroup per
 // environment, thread = gate column with its w_ih / w_hh column resident in
@@ -123,8 +124,9 @@ struct MountainCarContDyn {
   }
 };
 
-struct RolloutArgs {
-  // live policy weights (transposed layout, read by pointer every launch)
+// Live policy weights (transposed layout, read by pointer every launch):
+// what the training rollouts and the evaluation kernels have in common.
+struct PolicyWeights {
   const float* body_w;   // (F, H)
   const float* body_b;   // (H)
   const float* w_ih;     // (H, 4H)
@@ -132,6 +134,9 @@ struct RolloutArgs {
   const float* b_g;      // (4H)
   const float* heads_w;  // (H, D) — columns [0, A) are the logits head
   const float* heads_b;  // (D)
+};
+
+struct RolloutArgs : PolicyWeights {
   // persistent per-env state (read and written)
   float* env_state;      // (N, F)
   float* h;              // (N, H)
@@ -178,6 +183,16 @@ struct RecurrentCore {
   // Weight columns into registers; env n's carried h / c into LDS.
   __device__ __forceinline__ void load(const RolloutArgs& p, int tid, int n,
                                        float* s_h, float* s_c) {
+    load_weights(p, tid);
+    if (tid < H) {
+      s_h[tid] = p.h[(long)n * H + tid];
+      s_c[tid] = p.c[(long)n * H + tid];
+    }
+  }
+
+  // Weight columns into registers.
+  __device__ __forceinline__ void load_weights(const PolicyWeights& p,
+                                               int tid) {
     if constexpr (kWihRegs) {
 #pragma unroll
       for (int k = 0; k < H; ++k) wih[k] = p.w_ih[k * G + tid];
@@ -192,8 +207,6 @@ struct RecurrentCore {
 #pragma unroll
       for (int k = 0; k < F; ++k) bw[k] = p.body_w[k * H + tid];
       bb = p.body_b[tid];
-      s_h[tid] = p.h[(long)n * H + tid];
-      s_c[tid] = p.c[(long)n * H + tid];
     } else {
 #pragma unroll
       for (int k = 0; k < F; ++k) bw[k] = 0.0f;
@@ -207,11 +220,32 @@ struct RecurrentCore {
                                        const float* s_obs, const float* s_fir,
                                        float* s_xb, float* s_h, float* s_c,
                                        float* s_gates) {
-    if (tid < F) p.obs[row * F + tid] = s_obs[tid];
-    if (tid == 0) p.is_fir_out[row] = *s_fir;
+    step_impl<true>(p, tid, row, s_obs, s_fir, s_xb, s_h, s_c, s_gates);
+  }
+
+  // The advance part of step() alone — nothing is recorded (evaluation).
+  __device__ __forceinline__ void advance(const PolicyWeights& p, int tid,
+                                          const float* s_obs, float* s_xb,
+                                          float* s_h, float* s_c,
+                                          float* s_gates) {
+    step_impl<false>(p, tid, 0, s_obs, nullptr, s_xb, s_h, s_c, s_gates);
+  }
+
+  template <bool kRecord, typename Args>
+  __device__ __forceinline__ void step_impl(const Args& p, int tid, long row,
+                                            const float* s_obs,
+                                            const float* s_fir, float* s_xb,
+                                            float* s_h, float* s_c,
+                                            float* s_gates) {
+    if constexpr (kRecord) {
+      if (tid < F) p.obs[row * F + tid] = s_obs[tid];
+      if (tid == 0) p.is_fir_out[row] = *s_fir;
+    }
     if (tid < H) {
-      p.hx[row * H + tid] = s_h[tid];
-      p.cx[row * H + tid] = s_c[tid];
+      if constexpr (kRecord) {
+        p.hx[row * H + tid] = s_h[tid];
+        p.cx[row * H + tid] = s_c[tid];
+      }
       float acc = bb;
 #pragma unroll
       for (int k = 0; k < F; ++k) acc = fmaf(s_obs[k], bw[k], acc);
@@ -642,6 +676,340 @@ __global__ __launch_bounds__(4 * H) void rollout_gaussian(GaussianArgs p) {
   }
 }
 
+// ---- greedy evaluation: whole episodes in one launch ----------------------
+// rollout_eval_discrete / rollout_eval_gaussian run E episodes per env back
+// to back under the deterministic action (arg-max logit; tanh(mu)) and write
+// one return and one length per (env, episode). Geometry, weight residency
+// and the wave 0 / wave 1 overlap are those of the training kernels; what is
+// gone is everything a batch needs: no (N, S, ·) record, no softmax, no
+// log-prob, no sampling draw, no OU state — and nothing persistent is read or
+// written, so a launch cannot disturb the training envs. Episode e of env n
+// starts from Env::reset of hash tick e (lanes 1..draws) with h = c = 0, a
+// pure function of (seed, n, e); ``start_state`` may replace the start of
+// episode 0. An episode ends on ``terminated`` or at max_episode_steps.
+//
+// The step loop is bounded by E * max_episode_steps (every episode takes at
+// most max_episode_steps steps, so that many iterations finish all of them);
+// the workgroup-uniform control word in LDS only leaves it early.
+struct EvalArgs : PolicyWeights {
+  const float* start_state;  // (N, F) start of episode 0, or nullptr
+  float* ep_ret;             // (N, E)
+  int* ep_len;               // (N, E)
+  int N, E, D;
+  unsigned seed;
+  int max_episode_steps;
+};
+
+// control word written by thread 0 at the end of a step
+constexpr int kEvalGoOn = 0, kEvalNextEpisode = 1, kEvalAllDone = 2;
+
+template <int H, typename Env>
+__global__ __launch_bounds__(4 * H) void rollout_eval_discrete(EvalArgs p) {
+  constexpr int G = 4 * H;
+  constexpr int F = Env::kObsDim;
+  constexpr int A = Env::kActions;
+  static_assert(F <= 4, "reset draws use hash lanes 1..4");
+  const int tid = threadIdx.x;
+  const int n = blockIdx.x;
+  if (n >= p.N) return;  // uniform per workgroup
+
+  __shared__ __attribute__((aligned(16))) float s_xb[H];
+  __shared__ __attribute__((aligned(16))) float s_h[H];
+  __shared__ __attribute__((aligned(16))) float s_c[H];
+  __shared__ __attribute__((aligned(16))) float s_gates[G];
+  __shared__ float s_hw[A * H];  // logits head columns, [a][k]
+  __shared__ float s_obs[F];
+  __shared__ float s_cand[A * F];  // next state for every action
+  __shared__ float s_crew[A];
+  __shared__ int s_cterm[A];
+  __shared__ float s_ur[F];  // start state uniforms of the next episode
+  __shared__ int s_ctl;
+
+  RecurrentCore<H, F> core;
+  core.load_weights(p, tid);
+  float hb[A];
+#pragma unroll
+  for (int a = 0; a < A; ++a) hb[a] = p.heads_b[a];
+  for (int idx = tid; idx < A * H; idx += G) {
+    const int a = idx / H, k = idx % H;
+    s_hw[idx] = p.heads_w[k * p.D + a];
+  }
+  if (tid < H) {
+    s_h[tid] = 0.0f;
+    s_c[tid] = 0.0f;
+  }
+  if (tid == 0) {
+    float st[F];
+    if (p.start_state != nullptr) {
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = p.start_state[(long)n * F + k];
+    } else {
+      float u[F];
+#pragma unroll
+      for (int k = 0; k < F; ++k)
+        u[k] = pdrl_rng::uniform(p.seed, (unsigned)n, 0u, (unsigned)k + 1u);
+      Env::reset(st, u);
+    }
+#pragma unroll
+    for (int k = 0; k < F; ++k) s_obs[k] = st[k];
+  }
+  __syncthreads();
+
+  // every thread tracks the episode index (hash counter of the next start
+  // state); the step count and the running return live in thread 0
+  int episode = 0, steps = 0;
+  float run = 0.0f;
+  const int max_iters = p.E * p.max_episode_steps;  // <= 2^22 (binding)
+  for (int it = 0; it < max_iters; ++it) {
+    core.advance(p, tid, s_obs, s_xb, s_h, s_c, s_gates);
+
+    float lg[A];
+    if (tid < kWave) {
+      // logits: wave 0 splits the H-long dot products over its lanes and
+      // butterfly-reduces them, exactly as rollout_discrete does
+#pragma unroll
+      for (int a = 0; a < A; ++a) {
+        float part = 0.0f;
+        for (int k = tid; k < H; k += kWave)
+          part = fmaf(s_h[k], s_hw[a * H + k], part);
+#pragma unroll
+        for (int off = kWave / 2; off > 0; off >>= 1)
+          part += __shfl_xor(part, off, kWave);
+        lg[a] = part + hb[a];
+      }
+    } else if (tid < kWave + A) {
+      // meanwhile wave 1 steps the dynamics for every action (lane = action)
+      const int a = tid - kWave;
+      float st[F];
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+      float reward;
+      bool terminated;
+      Env::step(st, a, reward, terminated);
+#pragma unroll
+      for (int k = 0; k < F; ++k) s_cand[a * F + k] = st[k];
+      s_crew[a] = reward;
+      s_cterm[a] = terminated ? 1 : 0;
+    } else if (tid < kWave + A + F) {
+      // ... and draws the start state of the episode that would follow
+      const unsigned k = (unsigned)(tid - kWave - A);
+      s_ur[k] = pdrl_rng::uniform(p.seed, (unsigned)n,
+                                  (unsigned)episode + 1u, k + 1u);
+    }
+
+    // greedy action (thread 0 holds the reduced logits): strict > scan from
+    // action 0, so ties go to the lowest index
+    int chosen = 0;
+    if (tid == 0) {
+      float best = lg[0];
+#pragma unroll
+      for (int a = 1; a < A; ++a) {
+        if (lg[a] > best) {
+          best = lg[a];
+          chosen = a;
+        }
+      }
+    }
+    __syncthreads();
+
+    // the chosen action's outcome; episode end and fresh start (thread 0)
+    if (tid == 0) {
+      float st[F];
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = s_cand[chosen * F + k];
+      steps += 1;
+      run += s_crew[chosen];
+      const bool done = s_cterm[chosen] != 0 || steps >= p.max_episode_steps;
+      int ctl = kEvalGoOn;
+      if (done) {
+        p.ep_ret[(long)n * p.E + episode] = run;
+        p.ep_len[(long)n * p.E + episode] = steps;
+        Env::reset(st, s_ur);
+        steps = 0;
+        run = 0.0f;
+        ctl = (episode + 1 >= p.E) ? kEvalAllDone : kEvalNextEpisode;
+      }
+#pragma unroll
+      for (int k = 0; k < F; ++k) s_obs[k] = st[k];
+      s_ctl = ctl;
+    }
+    __syncthreads();
+    const int ctl = s_ctl;  // the same value in every thread of the workgroup
+    if (ctl == kEvalAllDone) break;
+    if (ctl == kEvalNextEpisode) {
+      episode += 1;
+      // thread j is the only reader of s_h[j] / s_c[j] before the next barrier
+      if (tid < H) {
+        s_h[tid] = 0.0f;
+        s_c[tid] = 0.0f;
+      }
+    }
+  }
+}
+
+template <int H, typename Env>
+__global__ __launch_bounds__(4 * H) void rollout_eval_gaussian(EvalArgs p) {
+  static_assert(Env::kActDim == 1, "one action dimension (head column 0)");
+  static_assert(Env::kResetDraws >= 1 && Env::kResetDraws <= 4,
+                "reset draws use hash lanes 1..4");
+  constexpr int F = Env::kObsDim;
+  constexpr int R = Env::kResetDraws;
+  constexpr int G = 4 * H;
+  const int tid = threadIdx.x;
+  const int n = blockIdx.x;
+  if (n >= p.N) return;  // uniform per workgroup
+
+  __shared__ __attribute__((aligned(16))) float s_xb[H];
+  __shared__ __attribute__((aligned(16))) float s_h[H];
+  __shared__ __attribute__((aligned(16))) float s_c[H];
+  __shared__ __attribute__((aligned(16))) float s_gates[G];
+  __shared__ float s_hw[H];  // mu head column
+  __shared__ float s_obs[F];
+  __shared__ float s_ur[R];  // start state uniforms of the next episode
+  __shared__ float s_drift;
+  __shared__ int s_ctl;
+
+  RecurrentCore<H, F> core;
+  core.load_weights(p, tid);
+  const float hb = p.heads_b[0];
+  if (tid < H) {
+    s_hw[tid] = p.heads_w[tid * p.D];
+    s_h[tid] = 0.0f;
+    s_c[tid] = 0.0f;
+  }
+  if (tid == 0) {
+    float st[F];
+    if (p.start_state != nullptr) {
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = p.start_state[(long)n * F + k];
+    } else {
+      float u[R];
+#pragma unroll
+      for (int k = 0; k < R; ++k)
+        u[k] = pdrl_rng::uniform(p.seed, (unsigned)n, 0u, (unsigned)k + 1u);
+      Env::reset(st, u);
+    }
+#pragma unroll
+    for (int k = 0; k < F; ++k) s_obs[k] = st[k];
+  }
+  __syncthreads();
+
+  int episode = 0, steps = 0;
+  float run = 0.0f;
+  const int max_iters = p.E * p.max_episode_steps;  // <= 2^22 (binding)
+  for (int it = 0; it < max_iters; ++it) {
+    core.advance(p, tid, s_obs, s_xb, s_h, s_c, s_gates);
+
+    float mu = 0.0f;
+    if (tid < kWave) {
+      // the mu head column only: wave 0 butterfly-reduces the dot product
+      float part = 0.0f;
+      for (int k = tid; k < H; k += kWave)
+        part = fmaf(s_h[k], s_hw[k], part);
+#pragma unroll
+      for (int off = kWave / 2; off > 0; off >>= 1)
+        part += __shfl_xor(part, off, kWave);
+      mu = part + hb;
+    } else if (tid == kWave) {
+      // meanwhile wave 1 evaluates the action-independent drift
+      float st[F];
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+      s_drift = Env::drift(st);
+    } else if (tid < kWave + 1 + R) {
+      // ... and draws the start state of the episode that would follow
+      const unsigned k = (unsigned)(tid - kWave - 1);
+      s_ur[k] = pdrl_rng::uniform(p.seed, (unsigned)n,
+                                  (unsigned)episode + 1u, k + 1u);
+    }
+    // deterministic action of both head schemes: the mean of PPO-C's
+    // Normal(tanh(mu), ·) and of SAC-C's squashed Gaussian at zero noise
+    float act = 0.0f;
+    if (tid == 0) act = tanhf(mu);
+    __syncthreads();
+
+    // env step, episode end and fresh start (thread 0)
+    if (tid == 0) {
+      float st[F];
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+      float reward;
+      bool terminated;
+      Env::step(st, act, s_drift, reward, terminated);
+      steps += 1;
+      run += reward;
+      const bool done = terminated || steps >= p.max_episode_steps;
+      int ctl = kEvalGoOn;
+      if (done) {
+        p.ep_ret[(long)n * p.E + episode] = run;
+        p.ep_len[(long)n * p.E + episode] = steps;
+        Env::reset(st, s_ur);
+        steps = 0;
+        run = 0.0f;
+        ctl = (episode + 1 >= p.E) ? kEvalAllDone : kEvalNextEpisode;
+      }
+#pragma unroll
+      for (int k = 0; k < F; ++k) s_obs[k] = st[k];
+      s_ctl = ctl;
+    }
+    __syncthreads();
+    const int ctl = s_ctl;  // the same value in every thread of the workgroup
+    if (ctl == kEvalAllDone) break;
+    if (ctl == kEvalNextEpisode) {
+      episode += 1;
+      // thread j is the only reader of s_h[j] / s_c[j] before the next barrier
+      if (tid < H) {
+        s_h[tid] = 0.0f;
+        s_c[tid] = 0.0f;
+      }
+    }
+  }
+}
+
+template <typename Env>
+void launch_eval_discrete(const EvalArgs& a, int H) {
+  const dim3 grid(a.N);
+  switch (H) {
+    case 32:
+      hipLaunchKernelGGL((rollout_eval_discrete<32, Env>), grid, dim3(128), 0,
+                         current_stream(), a);
+      break;
+    case 64:
+      hipLaunchKernelGGL((rollout_eval_discrete<64, Env>), grid, dim3(256), 0,
+                         current_stream(), a);
+      break;
+    case 128:
+      hipLaunchKernelGGL((rollout_eval_discrete<128, Env>), grid, dim3(512), 0,
+                         current_stream(), a);
+      break;
+    default:
+      TORCH_CHECK(false, "hidden size ", H, " unsupported (32/64/128)");
+  }
+  HIP_CHECK_LAST();
+}
+
+template <typename Env>
+void launch_eval_gaussian(const EvalArgs& a, int H) {
+  const dim3 grid(a.N);
+  switch (H) {
+    case 32:
+      hipLaunchKernelGGL((rollout_eval_gaussian<32, Env>), grid, dim3(128), 0,
+                         current_stream(), a);
+      break;
+    case 64:
+      hipLaunchKernelGGL((rollout_eval_gaussian<64, Env>), grid, dim3(256), 0,
+                         current_stream(), a);
+      break;
+    case 128:
+      hipLaunchKernelGGL((rollout_eval_gaussian<128, Env>), grid, dim3(512), 0,
+                         current_stream(), a);
+      break;
+    default:
+      TORCH_CHECK(false, "hidden size ", H, " unsupported (32/64/128)");
+  }
+  HIP_CHECK_LAST();
+}
+
 template <int H, typename Env>
 void launch_gaussian_mode(const GaussianArgs& a, int mode) {
   const dim3 grid(a.N), block(4 * H);
@@ -701,9 +1069,42 @@ void check_f32(const at::Tensor& t, long n, const char* name) {
               " elements");
 }
 
-// Argument checks and pointer packing shared by both entry points. The env
-// fixes obs_dim (F_env, else env_msg is raised) and A, the width of the
-// ``logits`` field and the number of leading head columns the kernel reads.
+// Checks and pointer packing of the live policy weights, shared by every
+// entry point. The env fixes obs_dim (F_env, else env_msg is raised) and A,
+// the number of leading head columns the kernel reads.
+PolicyWeights pack_policy_weights(
+    const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
+    const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
+    const at::Tensor& heads_b, long F_env, const char* env_msg, long A) {
+  CHECK_IN(body_w); CHECK_IN(body_b); CHECK_IN(w_ih); CHECK_IN(w_hh);
+  CHECK_IN(b_g); CHECK_IN(heads_w); CHECK_IN(heads_b);
+  TORCH_CHECK(body_w.dim() == 2 && w_ih.dim() == 2 && heads_w.dim() == 2,
+              "rollout: bad tensor ranks");
+  const long F = body_w.size(0), H = body_w.size(1), D = heads_w.size(1);
+  TORCH_CHECK(F == F_env, env_msg);
+  TORCH_CHECK(D >= A && heads_w.size(0) == H, "heads_w shape");
+  check_f32(body_b, H, "body_b");
+  check_f32(w_ih, H * 4 * H, "w_ih");
+  check_f32(w_hh, H * 4 * H, "w_hh");
+  check_f32(b_g, 4 * H, "b_g");
+  check_f32(heads_b, D, "heads_b");
+  const auto dev = body_w.device();
+  for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{
+        &body_b, &w_ih, &w_hh, &b_g, &heads_w, &heads_b})
+    TORCH_CHECK(t->device() == dev, "rollout: tensors on different devices");
+  PolicyWeights w;
+  w.body_w = body_w.data_ptr<float>();
+  w.body_b = body_b.data_ptr<float>();
+  w.w_ih = w_ih.data_ptr<float>();
+  w.w_hh = w_hh.data_ptr<float>();
+  w.b_g = b_g.data_ptr<float>();
+  w.heads_w = heads_w.data_ptr<float>();
+  w.heads_b = heads_b.data_ptr<float>();
+  return w;
+}
+
+// Argument checks and pointer packing shared by both training entry points;
+// A is also the width of the ``logits`` field.
 RolloutArgs pack_rollout_args(
     const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
     const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
@@ -714,21 +1115,14 @@ RolloutArgs pack_rollout_args(
     at::Tensor& is_fir_out, at::Tensor& hx, at::Tensor& cx,
     at::Tensor& ep_ret, long F_env, const char* env_msg, long A, long seed,
     long time_horizon, long max_episode_steps) {
-  CHECK_IN(body_w); CHECK_IN(body_b); CHECK_IN(w_ih); CHECK_IN(w_hh);
-  CHECK_IN(b_g); CHECK_IN(heads_w); CHECK_IN(heads_b);
-  TORCH_CHECK(body_w.dim() == 2 && w_ih.dim() == 2 && heads_w.dim() == 2 &&
-                  env_state.dim() == 2 && obs.dim() == 3,
+  RolloutArgs a;
+  static_cast<PolicyWeights&>(a) = pack_policy_weights(
+      body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, F_env, env_msg, A);
+  TORCH_CHECK(env_state.dim() == 2 && obs.dim() == 3,
               "rollout: bad tensor ranks");
   const long F = body_w.size(0), H = body_w.size(1), D = heads_w.size(1);
   const long N = env_state.size(0), S = obs.size(1);
-  TORCH_CHECK(F == F_env, env_msg);
   TORCH_CHECK(N >= 1 && S >= 1, "rollout: empty batch");
-  TORCH_CHECK(D >= A && heads_w.size(0) == H, "heads_w shape");
-  check_f32(body_b, H, "body_b");
-  check_f32(w_ih, H * 4 * H, "w_ih");
-  check_f32(w_hh, H * 4 * H, "w_hh");
-  check_f32(b_g, 4 * H, "b_g");
-  check_f32(heads_b, D, "heads_b");
   check_f32(env_state, N * F, "env_state");
   check_f32(h, N * H, "h");
   check_f32(c, N * H, "c");
@@ -747,21 +1141,12 @@ RolloutArgs pack_rollout_args(
   check_f32(ep_ret, N * S, "ep_ret");
   const auto dev = body_w.device();
   for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{
-        &body_b, &w_ih, &w_hh, &b_g, &heads_w, &heads_b, &env_state, &h, &c,
-        &is_fir, &ep_steps, &ep_run, &tick, &obs, &act, &rew, &logits,
-        &log_prob, &is_fir_out, &hx, &cx, &ep_ret})
+        &env_state, &h, &c, &is_fir, &ep_steps, &ep_run, &tick, &obs, &act,
+        &rew, &logits, &log_prob, &is_fir_out, &hx, &cx, &ep_ret})
     TORCH_CHECK(t->device() == dev, "rollout: tensors on different devices");
   TORCH_CHECK(time_horizon >= 1 && max_episode_steps >= 1,
               "rollout: horizons must be positive");
 
-  RolloutArgs a;
-  a.body_w = body_w.data_ptr<float>();
-  a.body_b = body_b.data_ptr<float>();
-  a.w_ih = w_ih.data_ptr<float>();
-  a.w_hh = w_hh.data_ptr<float>();
-  a.b_g = b_g.data_ptr<float>();
-  a.heads_w = heads_w.data_ptr<float>();
-  a.heads_b = heads_b.data_ptr<float>();
   a.env_state = env_state.data_ptr<float>();
   a.h = h.data_ptr<float>();
   a.c = c.data_ptr<float>();
@@ -784,6 +1169,53 @@ RolloutArgs pack_rollout_args(
   a.seed = (unsigned)seed;
   a.time_horizon = (int)std::min<long>(time_horizon, INT32_MAX);
   a.max_episode_steps = (int)std::min<long>(max_episode_steps, INT32_MAX);
+  return a;
+}
+
+// Upper bound of the evaluation kernels' step loop, E * max_episode_steps.
+constexpr long kEvalMaxIters = 1L << 22;
+
+// Argument checks and pointer packing of the evaluation entry points.
+// ep_ret (N, E) fixes the number of envs and of episodes per env.
+EvalArgs pack_eval_args(
+    const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
+    const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
+    const at::Tensor& heads_b, at::Tensor& ep_ret, at::Tensor& ep_len,
+    const c10::optional<at::Tensor>& start_state, long F_env,
+    const char* env_msg, long A, long seed, long max_episode_steps) {
+  EvalArgs a;
+  static_cast<PolicyWeights&>(a) = pack_policy_weights(
+      body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, F_env, env_msg, A);
+  TORCH_CHECK(ep_ret.dim() == 2, "rollout_eval: ep_ret must be (N, E)");
+  const long N = ep_ret.size(0), E = ep_ret.size(1);
+  TORCH_CHECK(N >= 1 && N <= INT32_MAX, "rollout_eval: bad number of envs");
+  TORCH_CHECK(E >= 1, "rollout_eval: episodes must be positive");
+  TORCH_CHECK(max_episode_steps >= 1,
+              "rollout_eval: max_episode_steps must be positive");
+  TORCH_CHECK(E <= kEvalMaxIters && max_episode_steps <= kEvalMaxIters &&
+                  E * max_episode_steps <= kEvalMaxIters,
+              "rollout_eval: episodes * max_episode_steps = ", E, " * ",
+              max_episode_steps, " exceeds the step loop bound ",
+              kEvalMaxIters);
+  check_f32(ep_ret, N * E, "ep_ret");
+  check_i32(ep_len, N * E, "ep_len");
+  const auto dev = body_w.device();
+  TORCH_CHECK(ep_ret.device() == dev && ep_len.device() == dev,
+              "rollout: tensors on different devices");
+  a.start_state = nullptr;
+  if (start_state.has_value()) {
+    check_f32(*start_state, N * F_env, "start_state");
+    TORCH_CHECK(start_state->device() == dev,
+                "rollout: tensors on different devices");
+    a.start_state = start_state->data_ptr<float>();
+  }
+  a.ep_ret = ep_ret.data_ptr<float>();
+  a.ep_len = ep_len.data_ptr<int>();
+  a.N = (int)N;
+  a.E = (int)E;
+  a.D = (int)heads_w.size(1);
+  a.seed = (unsigned)seed;
+  a.max_episode_steps = (int)max_episode_steps;
   return a;
 }
 
@@ -870,6 +1302,50 @@ void rollout_gaussian_hip(
     case 1:
       launch_gaussian<MountainCarContDyn>(a, (int)body_w.size(1), (int)mode);
       break;
+  }
+}
+
+// Greedy evaluation, discrete policy: E = ep_ret.size(1) whole episodes per
+// env in one launch. env_id as in rollout_discrete_hip.
+void rollout_eval_discrete_hip(
+    const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
+    const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
+    const at::Tensor& heads_b, at::Tensor& ep_ret, at::Tensor& ep_len,
+    const c10::optional<at::Tensor>& start_state, long env_id, long seed,
+    long max_episode_steps) {
+  switch (env_id) {
+    case 0: {
+      const EvalArgs a = pack_eval_args(
+          body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, ep_ret, ep_len,
+          start_state, CartPoleDyn::kObsDim, "CartPole needs obs_dim 4",
+          CartPoleDyn::kActions, seed, max_episode_steps);
+      launch_eval_discrete<CartPoleDyn>(a, (int)body_w.size(1));
+      break;
+    }
+    default:
+      TORCH_CHECK(false, "rollout: unknown device env id ", env_id);
+  }
+}
+
+// Greedy evaluation, Gaussian policy: the action is tanh(mu) for both head
+// schemes, so only head column 0 is read. env_id as in rollout_gaussian_hip.
+void rollout_eval_gaussian_hip(
+    const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
+    const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
+    const at::Tensor& heads_b, at::Tensor& ep_ret, at::Tensor& ep_len,
+    const c10::optional<at::Tensor>& start_state, long env_id, long seed,
+    long max_episode_steps) {
+  switch (env_id) {
+    case 1: {
+      const EvalArgs a = pack_eval_args(
+          body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, ep_ret, ep_len,
+          start_state, MountainCarContDyn::kObsDim,
+          "MountainCarContinuous needs obs_dim 2", 1, seed, max_episode_steps);
+      launch_eval_gaussian<MountainCarContDyn>(a, (int)body_w.size(1));
+      break;
+    }
+    default:
+      TORCH_CHECK(false, "rollout: unknown continuous device env id ", env_id);
   }
 }
 

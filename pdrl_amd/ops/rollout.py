@@ -44,6 +44,9 @@ cpu_actor.cpp::act_batch_gaussian; ``logits`` is ``[mu_raw | second_raw]``):
                                  - log(1 - act² + 1e-7)
 
 Env state is NOT checkpointed: a resumed run starts fresh episodes.
+
+Greedy evaluation of the same cores on the same dynamics — whole episodes,
+deterministic action, no batch — is the sibling ops/evaluate.py.
 """
 from __future__ import annotations
 

@@ -9,7 +9,11 @@ synchronize, 50 warm-up calls, timed windows of at least ``--window`` s.
     and ``--mode resident`` (the ceiling: no data path at all);
 (c) the Gaussian ``rollout()`` alone on MountainCarContinuous-v0, both
     sampling schemes (mode 0 = PPO-C, 1 = SAC-C), at N=128 and N=1024;
-(d) rollout + PPO-Continuous update in device mode at B=128.
+(d) rollout + PPO-Continuous update in device mode at B=128;
+(e) one greedy ``evaluate()`` call (whole episodes, untrained policy) on
+    CartPole-v1 (8 episodes per env) and MountainCarContinuous-v0 (1
+    episode of 999 steps) at N=64 and N=1024: ``ms_per_call`` and, since
+    the envs run side by side, ``us_per_step`` of the longest env.
 
 Prints one JSON line per measurement; ``values`` holds every repeat.
 """
@@ -138,6 +142,31 @@ def main():
     games, mean50 = ro.episode_stats()
     report("device_mode_ppoc", vals, batch_size=p.batch_size, seq_len=S,
            hidden=H, episodes=games, mean50=mean50)
+
+    # (e) one greedy evaluate() call: whole episodes in one launch. The envs
+    # run side by side, so the call lasts as long as its longest env:
+    # us_per_step = call time / the largest per-env step count
+    from pdrl_amd.ops.evaluate import DeviceEvaluator
+
+    for env, cls, dims, episodes in ((
+            "CartPole-v1", MlpLSTMSingle, (4, 2), 8), (
+            cenv, MlpLSTMSeperateContinuous, (2, 1), 1)):
+        for n_envs in (64, 1024):
+            torch.manual_seed(0)
+            model = cls(*dims, S, H).to(dev)
+            ev = DeviceEvaluator(model.actor.core, env, n_envs, episodes, dev,
+                                 seed=4321)
+            for _ in range(5):
+                ev.evaluate()
+            per_env = ev.lengths.sum(1)
+            steps, longest = int(per_env.sum()), int(per_env.max())
+            vals = [timed(ev.evaluate, args.window, steps, 20)
+                    for _ in range(args.repeats)]
+            ms = sorted(steps / v * 1e3 for v in vals)[len(vals) // 2]
+            report("evaluate_call", vals, env=env, num_envs=n_envs,
+                   episodes=episodes, hidden=H, env_steps=steps,
+                   longest_env_steps=longest, ms_per_call=ms,
+                   us_per_step=ms * 1e3 / longest, **ev.summary())
 
 
 if __name__ == "__main__":

@@ -43,7 +43,11 @@ def free_port_pair(excl=()):
     raise RuntimeError("no free port pair")
 
 
-def read_reward_curve(result_dir: Path):
+TRAIN_METRIC = "50-game-mean-stat-of-epi-rew"  # sampling policy, training envs
+EVAL_METRIC = "eval-mean-return"  # greedy policy, fixed start states
+
+
+def read_reward_curve(result_dir: Path, tag: str = TRAIN_METRIC):
     curve = []
     f = result_dir / "scalars.jsonl"
     if not f.exists():
@@ -53,7 +57,7 @@ def read_reward_curve(result_dir: Path):
             rec = json.loads(line)
         except json.JSONDecodeError:
             continue
-        if rec.get("tag") == "50-game-mean-stat-of-epi-rew":
+        if rec.get("tag") == tag:
             curve.append((rec["wall"], rec["value"]))
     return curve
 
@@ -72,6 +76,10 @@ def main():
     ap.add_argument("--actor", choices=("workers", "device"), default="workers",
                     help="device: the learner rolls out on the GPU itself "
                          "(no manager / worker processes)")
+    ap.add_argument("--eval-interval", type=int, default=0,
+                    help="greedy device evaluation every N updates; --target "
+                         "is then judged on eval-mean-return (needs an env "
+                         "with device dynamics)")
     ap.add_argument("--set", action="append", default=[],
                     help="extra param override key=value (repeatable)")
     args = ap.parse_args()
@@ -92,6 +100,8 @@ def main():
     if args.batch_size is not None:
         base["batch_size"] = args.batch_size
     base["actor_mode"] = args.actor
+    if args.eval_interval > 0:
+        base["eval_interval"] = args.eval_interval
     for kv in args.set:
         k, v = kv.split("=", 1)
         try:
@@ -129,6 +139,8 @@ def main():
         spawn("worker_sub_process", args.workers, "127.0.0.1", "127.0.0.1", mgr_port, lrn_port)
 
     deadline = t0 + args.minutes * 60
+    # the params file decides (a --set eval_interval=N counts too)
+    metric = EVAL_METRIC if int(base.get("eval_interval") or 0) > 0 else TRAIN_METRIC
     result_dir = None
     best, reached = -1e9, None
     try:
@@ -141,7 +153,7 @@ def main():
                     result_dir = sorted(dirs)[-1]
             if result_dir is None:
                 continue
-            curve = read_reward_curve(result_dir)
+            curve = read_reward_curve(result_dir, metric)
             if curve:
                 rew = curve[-1][1]
                 best = max(best, rew)
@@ -169,8 +181,9 @@ def main():
     out = {
         "algo": args.algo, "env": args.env, "actor": args.actor,
         "workers": args.workers if args.actor == "workers" else 0,
-        "target": args.target, "time_to_target_s": reached,
-        "best_50_game_mean": best if best > -1e9 else None,
+        "target": args.target, "metric": metric, "time_to_target_s": reached,
+        ("best_50_game_mean" if metric == TRAIN_METRIC else "best_eval_mean_return"):
+            best if best > -1e9 else None,
         "elapsed_s": time.monotonic() - t0,
         "result_dir": str(result_dir) if result_dir else None,
     }
