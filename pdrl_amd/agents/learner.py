@@ -269,6 +269,11 @@ class Learner:
         self.updater = maybe_graph(self.updater, self.device)
 
         self.on_policy = is_on_policy(params.algo)
+        self.replay_kernel = getattr(params, "replay_kernel", "eager")
+        if self.replay_kernel not in ("eager", "fused"):
+            raise ValueError(
+                f"replay_kernel must be 'eager' or 'fused', got "
+                f"{self.replay_kernel!r}")
         self.device_rollout = None
         self.evaluator = None
         self.last_eval = None
@@ -286,12 +291,7 @@ class Learner:
         # the host ring becomes an ingest conveyor, sampling is device-side.
         self.device_replay = None
         if not self.on_policy and self.device.type == "cuda":
-            from pdrl_amd.buffers.device_replay import DeviceReplay
-
-            self.device_replay = DeviceReplay(
-                ring.field_dims, ring.seq_len, params.buffer_size, self.device,
-                seed=1234 + rank,
-            )
+            self.device_replay = self._make_replay(ring.field_dims, ring.seq_len)
 
         # weight plane: PUB bound at learner_port + 1 (rank 0 only)
         self.pub = pub_bind(learner_ip, learner_port + 1) if self.is_root else None
@@ -309,6 +309,17 @@ class Learner:
         self.writer = SummaryWriter(params.result_dir) if self.is_root else None
         self.timer = ExecutionTimer(num_transition=params.seq_len * params.batch_size * world_size)
         self._replay_ready = False  # latching (reference: learner.py:385)
+
+    def _make_replay(self, field_dims, seq_len):
+        """The off-policy replay in HBM: ``DeviceReplay`` (eager torch ops,
+        the default) or, with ``"replay_kernel": "fused"``, the one-launch
+        ``FusedDeviceReplay`` — same rings, hash-drawn sample slots."""
+        from pdrl_amd.buffers.device_replay import (DeviceReplay,
+                                                    FusedDeviceReplay)
+
+        cls = FusedDeviceReplay if self.replay_kernel == "fused" else DeviceReplay
+        return cls(field_dims, seq_len, self.params.buffer_size, self.device,
+                   seed=1234 + self.rank)
 
     def _actor_core(self):
         mods = self.updater.trainable_modules()
@@ -367,7 +378,8 @@ class Learner:
         bound), and the data is exactly on-policy: ``log_prob`` / ``logits``
         come from the weights the update is about to use. On-policy algos
         train on the rollout itself; SAC (discrete and continuous) appends
-        it to the ``DeviceReplay`` and samples. The policy kind must match
+        it to the device replay and samples (``_make_replay``; one launch
+        per update with ``"replay_kernel": "fused"``). The policy kind must match
         the env's action space. The ring is never read or written.
         Env state is not checkpointed: a resumed run starts fresh episodes.
         """
@@ -412,11 +424,8 @@ class Learner:
         self.is_root = self.rank == 0
         self.device_replay = None
         if not self.on_policy:
-            from pdrl_amd.buffers.device_replay import DeviceReplay
-
-            self.device_replay = DeviceReplay(
-                self.device_rollout.fields, p.seq_len, p.buffer_size,
-                self.device, seed=1234 + self.rank)
+            self.device_replay = self._make_replay(
+                self.device_rollout.fields, p.seq_len)
         self.pub = None
         self.weight_pub = None
         self.weight_pub_async = None
@@ -452,6 +461,13 @@ class Learner:
             batch = self.device_rollout.rollout()
             if self.device_replay is None:
                 return batch
+            if self.replay_kernel == "fused":
+                # warm-up pushes, then append + sample in one launch
+                b, n = self.params.batch_size, self.device_rollout.N
+                while self.device_replay.size + n < b:
+                    self.device_replay.append_batch(batch)
+                    batch = self.device_rollout.rollout()
+                return self.device_replay.push_sample(batch, b)
             self.device_replay.append_batch(batch)
             while self.device_replay.size < self.params.batch_size:  # warm-up
                 self.device_replay.append_batch(self.device_rollout.rollout())

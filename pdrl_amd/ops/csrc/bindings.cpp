@@ -57,6 +57,10 @@ void rollout_eval_gaussian_hip(
     const at::Tensor&, const at::Tensor&, const at::Tensor&, at::Tensor&,
     at::Tensor&, const c10::optional<at::Tensor>&, long, long, long);
 double rollout_uniform_host(long, long, long, long);
+void replay_push_sample_hip(const std::vector<at::Tensor>&,
+                            const std::vector<at::Tensor>&,
+                            const std::vector<at::Tensor>&, long, long, long,
+                            long, long, long, long);
 void seq_lstm_fwd_loss_hip(
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
@@ -288,6 +292,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rollout_uniform", &rollout_uniform_host,
         "host evaluation of the rollout's counter-hash uniform",
         py::arg("seed"), py::arg("env"), py::arg("tick"), py::arg("k"));
+  m.def("replay_push_sample", &replay_push_sample_hip,
+        "device replay: append n_push source rows to the per-field rings and "
+        "gather n_sample hash-drawn trajectories into out, in one launch "
+        "(observably push, then sample)",
+        py::arg("src"), py::arg("ring"), py::arg("out"), py::arg("n_push"),
+        py::arg("n_sample"), py::arg("head"), py::arg("capacity"),
+        py::arg("filled"), py::arg("draw"), py::arg("seed"));
   m.def("seq_lstm_fwd_loss", &seq_lstm_fwd_loss_hip,
         "forward + row-local loss (IMPALA/PPO/PPO-C, V-MPO pre) in ONE "
         "launch",

@@ -24,7 +24,9 @@ and 6 are the radius and the angle of a Gaussian policy's one standard normal
 
     n(seed, env, tick) = sqrt(-2 * log(1 - u5)) * cos(6.2831855 * u6)
 
-(``1 - u5`` is exact in fp32 and never 0); lane 7 is free. The initial state
+(``1 - u5`` is exact in fp32 and never 0); lane 7 is free here (the fused
+device replay draws its slots from it under a salted seed:
+buffers/device_replay.py). The initial state
 at construction uses tick 0. One normal per tick means one action dimension:
 more need a wider counter.
 
@@ -72,15 +74,22 @@ def _wang(s: torch.Tensor) -> torch.Tensor:
     return s
 
 
-def uniform(seed: int, env: torch.Tensor, tick, k: int) -> torch.Tensor:
-    """u(seed, env, tick, k) as fp32; ``env`` int64 tensor, ``tick`` an int
-    or an int64 tensor broadcastable against it."""
+def hash_bits(seed: int, env: torch.Tensor, tick, k: int) -> torch.Tensor:
+    """The raw 32 bits h(seed, env, tick, k) (csrc/rollout_rng.h::bits) as
+    int64 values in [0, 2^32); ``env`` int64 tensor, ``tick`` an int or an
+    int64 tensor broadcastable against it. The counter ``tick*8 + k`` is
+    uint32, so it wraps after 2^29 ticks."""
     env = env.to(torch.int64)
     if not torch.is_tensor(tick):
         tick = torch.full_like(env, int(tick))
     h0 = _wang((int(seed) & _M32) ^ ((env * 0x9E3779B1) & _M32))
     ctr = (tick.to(torch.int64) * 8 + int(k) + 0x85EBCA6B) & _M32
-    h = _wang(h0 ^ _wang(ctr))
+    return _wang(h0 ^ _wang(ctr))
+
+
+def uniform(seed: int, env: torch.Tensor, tick, k: int) -> torch.Tensor:
+    """u(seed, env, tick, k) as fp32; arguments as ``hash_bits``."""
+    h = hash_bits(seed, env, tick, k)
     return (h >> 8).to(torch.float32) * (1.0 / 16777216.0)
 
 

@@ -13,7 +13,16 @@ synchronize, 50 warm-up calls, timed windows of at least ``--window`` s.
 (e) one greedy ``evaluate()`` call (whole episodes, untrained policy) on
     CartPole-v1 (8 episodes per env) and MountainCarContinuous-v0 (1
     episode of 999 steps) at N=64 and N=1024: ``ms_per_call`` and, since
-    the envs run side by side, ``us_per_step`` of the longest env.
+    the envs run side by side, ``us_per_step`` of the longest env;
+(f) the device replay alone, CartPole SAC fields, N = B = 128, capacity
+    10240: ``append_batch`` + ``sample`` of ``DeviceReplay``
+    (``replay_kernel`` eager) against ``push_sample`` of
+    ``FusedDeviceReplay`` (fused); also ``us_per_call``;
+(g) rollout + replay + SAC / SAC-Continuous update in device mode at B=128
+    (``Learner.next_batch`` + ``updater.step``), once per ``replay_kernel``.
+    In (f) and (g) the two paths alternate inside one run.
+
+``--only-replay`` runs (f) and (g) alone.
 
 Prints one JSON line per measurement; ``values`` holds every repeat.
 """
@@ -56,15 +65,94 @@ def report(name: str, values: list[float], **cfg):
     }), flush=True)
 
 
+def replay_sections(args, dev: str, S: int, H: int):
+    """(f) and (g): the off-policy replay, eager ops against the fused
+    launch. Both paths are built first and timed alternately, repeat by
+    repeat, so drift of the machine hits them alike."""
+    import shutil
+    import tempfile
+
+    from pdrl_amd.agents import Learner
+    from pdrl_amd.buffers import rollout_fields
+    from pdrl_amd.buffers.device_replay import DeviceReplay, FusedDeviceReplay
+    from pdrl_amd.utils import load_params
+
+    def alternate(fns: dict, steps_per_call: int, chunk: int) -> dict:
+        for fn in fns.values():
+            for _ in range(WARMUP):
+                fn()
+        vals = {k: [] for k in fns}
+        for _ in range(args.repeats):
+            for k, fn in fns.items():
+                vals[k].append(timed(fn, args.window, steps_per_call, chunk))
+        return vals
+
+    def us_per_call(values: list[float], steps_per_call: int) -> float:
+        return steps_per_call / sorted(values)[len(values) // 2] * 1e6
+
+    # (f) replay alone
+    N = B = 128
+    fields = rollout_fields(4, 2, H, False)
+    torch.manual_seed(0)
+    batch = {k: torch.randn(N, S, d, device=dev) for k, d in fields.items()}
+    eager = DeviceReplay(fields, S, 10240, dev, seed=1234)
+    fused = FusedDeviceReplay(fields, S, 10240, dev, seed=1234)
+
+    def eager_call():
+        eager.append_batch(batch)
+        eager.sample(B)
+
+    vals = alternate({"eager": eager_call,
+                      "fused": lambda: fused.push_sample(batch, B)}, N * S, 200)
+    for kernel, v in vals.items():
+        report("replay_only", v, replay_kernel=kernel, num_push=N, batch_size=B,
+               seq_len=S, hidden=H, capacity=10240,
+               us_per_call=us_per_call(v, N * S))
+
+    # (g) rollout + replay + update, device mode, B=128
+    for algo, env, dims, cont, name in (
+            ("SAC", "CartPole-v1", (4, 2), False, "device_mode_sac"),
+            ("SAC-Continuous", "MountainCarContinuous-v0", (2, 1), True,
+             "device_mode_sacc")):
+        learners = {}
+        for kernel in ("eager", "fused"):
+            p = load_params()
+            p.algo, p.env, p.continuous = algo, env, cont
+            p.obs_dim, p.n_actions = dims
+            p.batch_size, p.seq_len, p.hidden_size = 128, S, H
+            p.actor_mode, p.replay_kernel = "device", kernel
+            p.result_dir = tempfile.mkdtemp(prefix="pdrl_bench_")
+            torch.manual_seed(1234)
+            learners[kernel] = Learner(None, "127.0.0.1", 0, p, device=dev)
+
+        def stepper(lrn):
+            return lambda: lrn.updater.step(lrn.next_batch())
+
+        vals = alternate({k: stepper(l) for k, l in learners.items()},
+                         128 * S, 100)
+        for kernel, v in vals.items():
+            report(name, v, replay_kernel=kernel, batch_size=128, seq_len=S,
+                   hidden=H, us_per_call=us_per_call(v, 128 * S),
+                   replay_size=learners[kernel].device_replay.size)
+        for lrn in learners.values():
+            lrn.close()
+            shutil.rmtree(lrn.params.result_dir, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--window", type=float, default=1.0)
     ap.add_argument("--seq-len", type=int, default=5)
     ap.add_argument("--hidden", type=int, default=64)
+    ap.add_argument("--only-replay", action="store_true",
+                    help="run the replay entries (f) and (g) alone")
     args = ap.parse_args()
 
     assert torch.cuda.is_available(), "needs a GPU"
+    if args.only_replay:
+        replay_sections(args, "cuda:0", args.seq_len, args.hidden)
+        return
     from pdrl_amd.agents.learner_module import ImpalaUpdater, PPOUpdater
     from pdrl_amd.networks import MlpLSTMSingle
     from pdrl_amd.networks.models import (MlpLSTMSeperateContinuous,
@@ -167,6 +255,9 @@ def main():
                    episodes=episodes, hidden=H, env_steps=steps,
                    longest_env_steps=longest, ms_per_call=ms,
                    us_per_step=ms * 1e3 / longest, **ev.summary())
+
+    # (f), (g) the off-policy replay: eager ops against the fused launch
+    replay_sections(args, dev, S, H)
 
 
 if __name__ == "__main__":

@@ -28,6 +28,7 @@ SRC = [
     "pdrl_amd/ops/csrc/multi_tensor.hip",
     "pdrl_amd/ops/csrc/fwd_loss.hip",
     "pdrl_amd/ops/csrc/rollout.hip",
+    "pdrl_amd/ops/csrc/replay.hip",
 ]
 
 setup(
