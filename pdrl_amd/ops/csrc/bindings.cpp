@@ -24,7 +24,21 @@ void seq_lstm_wgrad_out_hip(const at::Tensor&, const at::Tensor&,
                             const c10::optional<at::Tensor>&,
                             const c10::optional<at::Tensor>&,
                             const c10::optional<at::Tensor>&,
-                            const c10::optional<at::Tensor>&);
+                            const c10::optional<at::Tensor>&,
+                            const c10::optional<at::Tensor>&,
+                            const c10::optional<at::Tensor>&, long, long,
+                            double, double, double, double);
+void seq_lstm_row_step_hip(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, at::Tensor&, at::Tensor&,
+    const c10::optional<at::Tensor>&, at::Tensor&, at::Tensor&, long, double,
+    double, double, double, double, double, double, double, double, double,
+    double);
+long seq_lstm_row_step_lds_bytes(long, long, long);
 void seq_lstm_forward_multi_hip(const at::Tensor&, const at::Tensor&,
                                 const at::Tensor&, const at::Tensor&,
                                 const at::Tensor&, long, long, long, long);
@@ -233,7 +247,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dbody_w"), py::arg("dbody_b"), py::arg("db_g"),
         py::arg("dheads_w"), py::arg("dheads_b"), py::arg("norm_sq"),
         py::arg("x2") = c10::nullopt, py::arg("dbody2_w") = c10::nullopt,
-        py::arg("dbody2_b") = c10::nullopt);
+        py::arg("dbody2_b") = c10::nullopt,
+        // on-policy row step: reduce the per-row loss partials into the
+        // stats vector in one extra block
+        py::arg("stats_part") = c10::nullopt, py::arg("stats") = c10::nullopt,
+        py::arg("algo") = 0, py::arg("B") = 0, py::arg("cp") = 0.0,
+        py::arg("cv") = 0.0, py::arg("ce") = 0.0, py::arg("creg") = 0.0);
   m.def("seq_lstm_forward_multi", &seq_lstm_forward_multi_hip,
         "multi-network fused forward (device pointer tables; dual-body "
         "rows carry body2/x2 pointers)",
@@ -314,6 +333,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("creg"), py::arg("vm_lse") = c10::nullopt,
         py::arg("vm_logp") = c10::nullopt, py::arg("vm_adv") = c10::nullopt,
         py::arg("vm_td") = c10::nullopt);
+  m.def("seq_lstm_row_step", &seq_lstm_row_step_hip,
+        "forward + row-local loss + BPTT (IMPALA/PPO/PPO-C) in ONE launch",
+        py::arg("x"), py::arg("h0"), py::arg("c0"), py::arg("body_w"),
+        py::arg("body_b"), py::arg("w_ih"), py::arg("w_hh"), py::arg("b_g"),
+        py::arg("heads_w"), py::arg("heads_b"), py::arg("outs"),
+        py::arg("hS"), py::arg("cS"), py::arg("stash"), py::arg("act"),
+        py::arg("behav"), py::arg("rew"), py::arg("fir"), py::arg("gouts"),
+        py::arg("stats_part"), py::arg("norm_sq"), py::arg("dgates"),
+        py::arg("dxb"), py::arg("algo"), py::arg("gamma"), py::arg("lmbda"),
+        py::arg("rho_bar"), py::arg("rho_min"), py::arg("c_bar"),
+        py::arg("rew_scale"), py::arg("cp"), py::arg("cv"), py::arg("ce"),
+        py::arg("eps_clip"), py::arg("creg"));
+  m.def("seq_lstm_row_step_lds_bytes", &seq_lstm_row_step_lds_bytes,
+        "dynamic LDS one seq_lstm_row_step block needs (launch limit 64 KiB)",
+        py::arg("S"), py::arg("D"), py::arg("algo"));
   m.def("seq_lstm_bwd_fin", &seq_lstm_bwd_fin_hip,
         "BPTT backward + stat finalization (or V-MPO grad emission)",
         py::arg("gouts"), py::arg("stash"), py::arg("x"), py::arg("c0"),

@@ -40,7 +40,8 @@ __device__ __forceinline__ void seq_lstm_fwd_row(
     const float* __restrict__ x2 = nullptr,       // (B,S,F2) dual body
     const float* __restrict__ body2_w = nullptr,  // (F2,half)
     const float* __restrict__ body2_b = nullptr,  // (half)
-    int F2 = 0, int half = H) {
+    int F2 = 0, int half = H,
+    float* outs_lds = nullptr) {  // (S,D) LDS copy of this row's outs
   constexpr int G = 4 * H;
   const int tid = threadIdx.x;
 
@@ -148,16 +149,39 @@ __device__ __forceinline__ void seq_lstm_fwd_row(
       acc = fmaf(hv.w, heads_w[(4 * k + 3) * D + d], acc);
     }
     outs[((long)b * S + t) * D + d] = acc;
+    if (outs_lds != nullptr) outs_lds[idx] = acc;
   }
 }
 
 
-// Backward through heads + recurrence + body for one batch row.
+// Register-resident weight rows for the back-projections of BPTT: thread
+// (part, k) = (tid/H, tid%H) owns its quarter of rows k of w_ih / w_hh —
+// the reductions then run entirely on registers + dg4 LDS broadcasts
+// (no 131 KiB LDS staging, no staging barrier). Only ISSUES the loads: a
+// caller may put other work under their latency before it runs
+// seq_lstm_bwd_row_on, which pins the values where it first needs them.
+template <int H>
+__device__ __forceinline__ void seq_lstm_bwd_load_rows(
+    const float* __restrict__ w_ih,    // (H,4H)
+    const float* __restrict__ w_hh,    // (H,4H)
+    float (&wih_row)[H], float (&whh_row)[H]) {
+  constexpr int G = 4 * H;
+  const int part = threadIdx.x / H, kk = threadIdx.x % H;
+#pragma unroll
+  for (int gg = 0; gg < H; ++gg) {
+    wih_row[gg] = w_ih[(long)kk * G + part * H + gg];
+    whh_row[gg] = w_hh[(long)kk * G + part * H + gg];
+  }
+}
+
+// Backward through heads + recurrence + body for one batch row; with
+// kRowsLoaded the caller has already run seq_lstm_bwd_load_rows.
 // Emits per-(b,t) pre-activation gate grads (dgates) and pre-ReLU body grads
 // (dxb) consumed by the MFMA weight-gradient kernels (wgrad.hip), plus
 // dx / dh0 / dc0.
-template <int H>
-__device__ __forceinline__ void seq_lstm_bwd_row(
+template <int H, bool kRowsLoaded>
+__device__ __forceinline__ void seq_lstm_bwd_row_on(
+    float (&wih_row)[H], float (&whh_row)[H],
     const float* __restrict__ gouts,   // (B,S,D) head-output grads
     const float* __restrict__ ghS,     // (B,H) or nullptr
     const float* __restrict__ gcS,     // (B,H) or nullptr
@@ -186,16 +210,9 @@ __device__ __forceinline__ void seq_lstm_bwd_row(
   float* part_h = dxb_s + S * H;                      // (4, H) partial sums
   float* part_x = part_h + G;                         // (4, H)
 
-  // Register-resident weight rows for the back-projections: thread
-  // (part, k) = (tid/H, tid%H) owns its quarter of rows k of w_ih / w_hh —
-  // the reductions then run entirely on registers + dg4 LDS broadcasts
-  // (no 131 KiB LDS staging, no staging barrier).
   const int part = tid / H, kk = tid % H;
-  float wih_row[H], whh_row[H];
-#pragma unroll
-  for (int gg = 0; gg < H; ++gg) {
-    wih_row[gg] = w_ih[(long)kk * G + part * H + gg];
-    whh_row[gg] = w_hh[(long)kk * G + part * H + gg];
+  if constexpr (!kRowsLoaded) {
+    seq_lstm_bwd_load_rows<H>(w_ih, w_hh, wih_row, whh_row);
   }
   PDRL_PIN_REGS(wih_row, H);
   PDRL_PIN_REGS(whh_row, H);
@@ -314,3 +331,31 @@ __device__ __forceinline__ void seq_lstm_bwd_row(
   }
 }
 
+// Loads and all, for the launches that have nothing to put under the loads.
+template <int H>
+__device__ __forceinline__ void seq_lstm_bwd_row(
+    const float* __restrict__ gouts,   // (B,S,D) head-output grads
+    const float* __restrict__ ghS,     // (B,H) or nullptr
+    const float* __restrict__ gcS,     // (B,H) or nullptr
+    const float* __restrict__ stash,   // (B,S,7H)
+    const float* __restrict__ x,       // (B,S,F)
+    const float* __restrict__ c0,      // (B,H)
+    const float* __restrict__ body_w,  // (F,H)
+    const float* __restrict__ w_ih,    // (H,4H)
+    const float* __restrict__ w_hh,    // (H,4H)
+    const float* __restrict__ heads_w, // (H,D)
+    float* __restrict__ dx,            // (B,S,F) or nullptr (leaf input)
+    float* __restrict__ dh0,           // (B,H)   or nullptr
+    float* __restrict__ dc0,           // (B,H)   or nullptr
+    float* __restrict__ dgates,        // (B,S,4H) pre-activation, or nullptr
+    float* __restrict__ dxb,           // (B,S,H) pre-ReLU
+    int b, int S, int F, int D, long h0s, char* smem_raw,
+    const float* __restrict__ body2_w = nullptr,  // (F2,half) dual body
+    float* __restrict__ dx2 = nullptr,            // (B,S,F2) second-input grad
+    int F2 = 0, int half = H, bool accum_dx2 = false) {
+  float wih_row[H], whh_row[H];
+  seq_lstm_bwd_row_on<H, false>(wih_row, whh_row, gouts, ghS, gcS, stash, x,
+                                c0, body_w, w_ih, w_hh, heads_w, dx, dh0, dc0,
+                                dgates, dxb, b, S, F, D, h0s, smem_raw,
+                                body2_w, dx2, F2, half, accum_dx2);
+}

@@ -28,11 +28,18 @@ __device__ __forceinline__ float ms_huber_grad(float d) {
 
 // Row-local IMPALA/PPO loss for batch row b: categorical stats, V-trace or
 // TD+GAE scan, analytic packed head grads, per-row loss-stat partials.
+// The INPUTS (outs, act, behav, rew, fir) are read at row offset si, the
+// outputs (gouts, stats_part) are written at row b. By default the inputs
+// are the global (B, S, ...) arrays and si = b*S; with kRowView they are a
+// view of row b alone (si = 0): the row step (fwd_loss.hip) passes LDS copies
+// of the row's inputs, so neither lane 0's scan nor the gradient loop issues
+// a global load there.
 // stats_part: (B, 8) per-row loss partials [pl, vl, es, ravg/rsum, rg,
 // rmin, rmax] written with PLAIN stores — a per-launch accumulator would
 // funnel 5-7 atomics per block onto one cache line, which measured ~10 µs
 // at B=128 (the whole benefit of fusing the loss into the forward). The
 // consumer (onpolicy_stats_reduce below) reduces the B rows in parallel.
+template <bool kRowView = false>
 __device__ void onpolicy_loss_row(
     int algo, const float* __restrict__ outs, const float* __restrict__ act,
     const float* __restrict__ behav, const float* __restrict__ rew,
@@ -52,9 +59,10 @@ __device__ void onpolicy_loss_row(
   float* s_adv = s_w + S;                          // (T)
   float* s_ret = s_adv + S;                        // (T) vs (IMPALA) | td (PPO)
   const long sb = (long)b * S;
+  const long si = kRowView ? 0 : sb;  // row offset of the inputs
 
   if (tid < S) {
-    const float* z = outs + (sb + tid) * D;
+    const float* z = outs + (si + tid) * D;
     float m = z[0];
     for (int j = 1; j < A; ++j) m = fmaxf(m, z[j]);
     float s = 0.f;
@@ -65,7 +73,7 @@ __device__ void onpolicy_loss_row(
       const float lp = z[j] - l;
       h -= __expf(lp) * lp;
     }
-    s_logp[tid] = z[(int)act[sb + tid]] - l;
+    s_logp[tid] = z[(int)act[si + tid]] - l;
     s_lse[tid] = l;
     s_ent[tid] = h;
   }
@@ -77,60 +85,60 @@ __device__ void onpolicy_loss_row(
     if (algo == kAlgoImpala) {
       float acc = 0.f;
       for (int t = T - 1; t >= 0; --t) {
-        const float ratio = __expf(s_logp[t] - behav[sb + t]);
+        const float ratio = __expf(s_logp[t] - behav[si + t]);
         const float rho = fminf(fmaxf(ratio, rho_min), rho_bar);
         const float c = fminf(ratio, c_bar);
-        const float mask = 1.f - fir[sb + t + 1];
-        const float vt = outs[(sb + t) * D + A];
-        const float vn = outs[(sb + t + 1) * D + A];
+        const float mask = 1.f - fir[si + t + 1];
+        const float vt = outs[(si + t) * D + A];
+        const float vn = outs[(si + t + 1) * D + A];
         const float delta =
-            rho * (rew[sb + t] * rew_scale + gamma * mask * vn - vt);
+            rho * (rew[si + t] * rew_scale + gamma * mask * vn - vt);
         acc = fmaf(gamma * mask * c, acc, delta);
         s_w[t] = rho;
         s_ret[t] = vt + acc;
       }
       for (int t = 0; t < T; ++t) {
-        const float mask = 1.f - fir[sb + t + 1];
-        const float vnext = (t + 1 < T) ? s_ret[t + 1] : outs[(sb + T) * D + A];
-        s_adv[t] = s_w[t] * (rew[sb + t] * rew_scale + gamma * mask * vnext -
-                             outs[(sb + t) * D + A]);
+        const float mask = 1.f - fir[si + t + 1];
+        const float vnext = (t + 1 < T) ? s_ret[t + 1] : outs[(si + T) * D + A];
+        s_adv[t] = s_w[t] * (rew[si + t] * rew_scale + gamma * mask * vnext -
+                             outs[(si + t) * D + A]);
       }
       for (int t = 0; t < T; ++t) {
         pl -= s_logp[t] * s_adv[t];
-        vl += ms_huber(outs[(sb + t) * D + A] - s_ret[t]);
+        vl += ms_huber(outs[(si + t) * D + A] - s_ret[t]);
         es += s_ent[t];
         rs += s_w[t];
         for (int j = 0; j < A; ++j) {
-          const float z = outs[(sb + t) * D + j];
+          const float z = outs[(si + t) * D + j];
           rg = fmaf(z, z, rg);
         }
       }
     } else {  // PPO: TD target + GAE, clipped surrogate
       float run = 0.f;
       for (int t = T - 1; t >= 0; --t) {
-        const float mask = 1.f - fir[sb + t + 1];
-        const float tdv = rew[sb + t] * rew_scale +
-                          gamma * mask * outs[(sb + t + 1) * D + A];
-        const float delta = tdv - outs[(sb + t) * D + A];
+        const float mask = 1.f - fir[si + t + 1];
+        const float tdv = rew[si + t] * rew_scale +
+                          gamma * mask * outs[(si + t + 1) * D + A];
+        const float delta = tdv - outs[(si + t) * D + A];
         run = fmaf(gamma * lmbda * mask, run, delta);
         s_ret[t] = tdv;
         s_adv[t] = run;
       }
       float rmin = 1e30f, rmax = -1e30f;
       for (int t = 0; t < T; ++t) {
-        const float r = __expf(s_logp[t] - behav[sb + t]);
+        const float r = __expf(s_logp[t] - behav[si + t]);
         const float a = s_adv[t];
         const float s1 = r * a;
         const float s2 =
             fminf(fmaxf(r, 1.f - eps_clip), 1.f + eps_clip) * a;
         pl -= fminf(s1, s2);
-        vl += ms_huber(outs[(sb + t) * D + A] - s_ret[t]);
+        vl += ms_huber(outs[(si + t) * D + A] - s_ret[t]);
         es += s_ent[t];
         rs += r;
         rmin = fminf(rmin, r);
         rmax = fmaxf(rmax, r);
         for (int j = 0; j < A; ++j) {
-          const float z = outs[(sb + t) * D + j];
+          const float z = outs[(si + t) * D + j];
           rg = fmaf(z, z, rg);
         }
       }
@@ -156,7 +164,7 @@ __device__ void onpolicy_loss_row(
       g[j] = 0.f;
       continue;
     }
-    const float* z = outs + (sb + t) * D;
+    const float* z = outs + (si + t) * D;
     if (j == A) {
       g[A] = cv * ms_huber_grad(z[A] - s_ret[t]) * invN;
       continue;
@@ -165,7 +173,7 @@ __device__ void onpolicy_loss_row(
     if (algo == kAlgoImpala) {
       dlogp = -cp * s_adv[t] * invN;
     } else {
-      const float r = __expf(s_logp[t] - behav[sb + t]);
+      const float r = __expf(s_logp[t] - behav[si + t]);
       const float a_v = s_adv[t];
       const bool inside = (r > 1.f - eps_clip) && (r < 1.f + eps_clip);
       const float s1 = r * a_v;
@@ -177,7 +185,7 @@ __device__ void onpolicy_loss_row(
     const float H = s_ent[t];
     const float lp = z[j] - s_lse[t];
     const float pj = __expf(lp);
-    const int a = (int)act[sb + t];
+    const int a = (int)act[si + t];
     g[j] = dlogp * ((j == a ? 1.f : 0.f) - pj) + dH * (-pj * (lp + H)) +
            dreg * z[j];
   }
@@ -187,7 +195,9 @@ __device__ void onpolicy_loss_row(
 // Row-local PPO-Continuous loss (Gaussian tanh-mean policy; reference math:
 // networks/models.py:103-118 + ppo/learning.py). Packed heads
 // [mu | std | value], D = 2A+1.
-// Same per-row stats_part protocol as onpolicy_loss_row.
+// Same kRowView input views and per-row stats_part protocol as
+// onpolicy_loss_row.
+template <bool kRowView = false>
 __device__ inline void ppoc_loss_row(
     const float* __restrict__ outs, const float* __restrict__ act,
     const float* __restrict__ behav, const float* __restrict__ rew,
@@ -206,15 +216,16 @@ __device__ inline void ppoc_loss_row(
   float* s_adv = s_ent + S;                        // (T)
   float* s_ret = s_adv + S;                        // (T)
   const long sb = (long)b * S;
+  const long si = kRowView ? 0 : sb;  // row offset of the inputs
 
   if (tid < S) {
-    const float* z = outs + (sb + tid) * D;
+    const float* z = outs + (si + tid) * D;
     float lp = 0.f, h = 0.f;
     for (int j = 0; j < A; ++j) {
       const float mut = tanhf(z[j]);
       const float sig = ((z[A + j] > 20.f) ? z[A + j]
                                            : log1pf(__expf(z[A + j]))) + 1e-4f;
-      const float x = act[(sb + tid) * A + j];
+      const float x = act[(si + tid) * A + j];
       const float d = (x - mut) / sig;
       lp += -0.5f * d * d - __logf(sig) - kRowLogSqrt2Pi;
       h += __logf(sig) + kRowEntConst;
@@ -227,10 +238,10 @@ __device__ inline void ppoc_loss_row(
   if (tid == 0) {
     float run = 0.f;
     for (int t = T - 1; t >= 0; --t) {
-      const float mask = 1.f - fir[sb + t + 1];
-      const float tdv = rew[sb + t] * rew_scale +
-                        gamma * mask * outs[(sb + t + 1) * D + 2 * A];
-      const float delta = tdv - outs[(sb + t) * D + 2 * A];
+      const float mask = 1.f - fir[si + t + 1];
+      const float tdv = rew[si + t] * rew_scale +
+                        gamma * mask * outs[(si + t + 1) * D + 2 * A];
+      const float delta = tdv - outs[(si + t) * D + 2 * A];
       run = fmaf(gamma * lmbda * mask, run, delta);
       s_ret[t] = tdv;
       s_adv[t] = run;
@@ -238,18 +249,18 @@ __device__ inline void ppoc_loss_row(
     float pl = 0.f, vl = 0.f, es = 0.f, rs = 0.f, rg = 0.f;
     float rmin = 1e30f, rmax = -1e30f;
     for (int t = 0; t < T; ++t) {
-      const float r = __expf(s_logp[t] - behav[sb + t]);
+      const float r = __expf(s_logp[t] - behav[si + t]);
       const float a = s_adv[t];
       const float s1 = r * a;
       const float s2 = fminf(fmaxf(r, 1.f - eps_clip), 1.f + eps_clip) * a;
       pl -= fminf(s1, s2);
-      vl += ms_huber(outs[(sb + t) * D + 2 * A] - s_ret[t]);
+      vl += ms_huber(outs[(si + t) * D + 2 * A] - s_ret[t]);
       es += s_ent[t];
       rs += r;
       rmin = fminf(rmin, r);
       rmax = fmaxf(rmax, r);
       for (int j = 0; j < 2 * A; ++j) {
-        const float z = outs[(sb + t) * D + j];
+        const float z = outs[(si + t) * D + j];
         rg = fmaf(z, z, rg);
       }
     }
@@ -274,21 +285,21 @@ __device__ inline void ppoc_loss_row(
       continue;
     }
     const float a_v = s_adv[t];
-    const float r = __expf(s_logp[t] - behav[sb + t]);
+    const float r = __expf(s_logp[t] - behav[si + t]);
     const bool inside = (r > 1.f - eps_clip) && (r < 1.f + eps_clip);
     const float s1 = r * a_v;
     const float s2 = fminf(fmaxf(r, 1.f - eps_clip), 1.f + eps_clip) * a_v;
     const float gr = (inside || s1 < s2) ? a_v * r : 0.f;
     const float dlogp = -cp * gr * invN;
     const float dH = -ce * invN;
-    const float* z = outs + (sb + t) * D;
+    const float* z = outs + (si + t) * D;
     if (j == 2 * A) {
       g[j] = cv * ms_huber_grad(z[2 * A] - s_ret[t]) * invN;
     } else if (j < A) {
       const float mut = tanhf(z[j]);
       const float sig = ((z[A + j] > 20.f) ? z[A + j]
                                            : log1pf(__expf(z[A + j]))) + 1e-4f;
-      const float x = act[(sb + t) * A + j];
+      const float x = act[(si + t) * A + j];
       const float diff = x - mut;
       const float dl_dmut = diff / (sig * sig);
       g[j] = dlogp * dl_dmut * (1.f - mut * mut) + dreg * z[j];
@@ -296,7 +307,7 @@ __device__ inline void ppoc_loss_row(
       const int jj = j - A;
       const float mut = tanhf(z[jj]);
       const float sig = ((z[j] > 20.f) ? z[j] : log1pf(__expf(z[j]))) + 1e-4f;
-      const float x = act[(sb + t) * A + jj];
+      const float x = act[(si + t) * A + jj];
       const float diff = x - mut;
       const float dl_dsig = diff * diff / (sig * sig * sig) - 1.0f / sig;
       const float dH_dsig = 1.0f / sig;
@@ -396,8 +407,10 @@ __device__ inline void vmpo_grad_row(
 
 // ---- what a row's block runs once the row's forward outputs exist:
 // block 0 zeroes norm_sq (its next writer, the wgrad kernel, runs in a
-// LATER launch), then the algorithm's row-local loss phase. D is the packed
-// head width (A+1, or 2A+1 for PPO-C); smem holds 6*S floats.
+// LATER launch), then the algorithm's row-local loss phase. kRowView: the
+// inputs are views of row b alone (V-MPO's pre-phase has no such form). D is
+// the packed head width (A+1, or 2A+1 for PPO-C); smem holds 6*S floats.
+template <bool kRowView = false>
 __device__ __forceinline__ void onpolicy_loss_phase(
     int algo, const float* __restrict__ outs, const float* __restrict__ act,
     const float* __restrict__ behav, const float* __restrict__ rew,
@@ -410,16 +423,19 @@ __device__ __forceinline__ void onpolicy_loss_phase(
     float eps_clip, float creg, char* smem) {
   if (b == 0 && threadIdx.x == 0 && norm_sq != nullptr) *norm_sq = 0.f;
   if (algo == kAlgoVmpo) {  // log-softmax + GAE to global scratch
-    vmpo_pre_row(outs, act, rew, fir, vm_lse, vm_logp, vm_adv, vm_td, b, S,
-                 D - 1, gamma, lmbda, rew_scale);
+    if constexpr (!kRowView) {
+      vmpo_pre_row(outs, act, rew, fir, vm_lse, vm_logp, vm_adv, vm_td, b, S,
+                   D - 1, gamma, lmbda, rew_scale);
+    }
   } else if (algo == kAlgoPpoC) {  // Gaussian tanh-mean policy
-    ppoc_loss_row(outs, act, behav, rew, fir, gouts, stats_part, b, B, S,
-                  (D - 1) / 2, gamma, lmbda, rew_scale, cp, cv, ce,
-                  eps_clip, creg, smem);
+    ppoc_loss_row<kRowView>(outs, act, behav, rew, fir, gouts, stats_part, b,
+                            B, S, (D - 1) / 2, gamma, lmbda, rew_scale, cp,
+                            cv, ce, eps_clip, creg, smem);
   } else {
-    onpolicy_loss_row(algo, outs, act, behav, rew, fir, gouts, stats_part,
-                      b, B, S, D - 1, gamma, lmbda, rho_bar, rho_min, c_bar,
-                      rew_scale, cp, cv, ce, eps_clip, creg, smem);
+    onpolicy_loss_row<kRowView>(algo, outs, act, behav, rew, fir, gouts,
+                                stats_part, b, B, S, D - 1, gamma, lmbda,
+                                rho_bar, rho_min, c_bar, rew_scale, cp, cv,
+                                ce, eps_clip, creg, smem);
   }
 }
 

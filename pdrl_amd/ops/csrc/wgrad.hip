@@ -14,13 +14,17 @@
 // The small gradients (body/head weights + all biases) are K=B·S reductions
 // with one WAVE per output element (lane-strided loads + shuffle reduce).
 #include "common.h"
+#include "loss_row.h"
 #include "wgrad_body.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace {
 
-template <int H>
+// kReduce: the launch carries the stats-reduce block of the on-policy row
+// step; without it the kernel is the plain weight-gradient sweep.
+template <int H, bool kReduce>
 __global__ __launch_bounds__(256) void wgrad_gates_mfma_kernel(
     const float* __restrict__ stash, const float* __restrict__ h0,
     const float* __restrict__ dgates, float* __restrict__ dw_ih,
@@ -30,7 +34,20 @@ __global__ __launch_bounds__(256) void wgrad_gates_mfma_kernel(
     float* __restrict__ dbody_b, float* __restrict__ db_g,
     float* __restrict__ dheads_w, float* __restrict__ dheads_b, int F, int D,
     int N, int S, long h0s, const float* __restrict__ x2, int F2,
-    float* __restrict__ dbody2_w, float* __restrict__ dbody2_b, int half) {
+    float* __restrict__ dbody2_w, float* __restrict__ dbody2_b, int half,
+    int reduce_block, const float* __restrict__ stats_part,
+    float* __restrict__ stats, int algo, int B, float cp, float cv, float ce,
+    float creg) {
+  // On-policy row step: ONE extra block (reduce_block, the last one; -1 for
+  // none) reduces the per-row loss partials an earlier launch stored into the
+  // final stats vector.
+  if constexpr (kReduce) {
+    if ((int)blockIdx.x == reduce_block) {
+      onpolicy_stats_reduce(stats_part, stats, algo, B, S, D, cp, cv, ce,
+                            creg);
+      return;
+    }
+  }
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   wgrad_gates_body<H>(stash, h0, dgates, dw_ih, dw_hh, norm_sq, x, dxb, gouts,
                       dbody_w, dbody_b, db_g, dheads_w, dheads_b, F, D, N, S,
@@ -75,7 +92,10 @@ void launch_wgrad(const at::Tensor& x, const at::Tensor& h0,
                   int N, int S, int F, int D,
                   const c10::optional<at::Tensor>& x2 = c10::nullopt,
                   at::Tensor* dbody2_w = nullptr,
-                  at::Tensor* dbody2_b = nullptr) {
+                  at::Tensor* dbody2_b = nullptr,
+                  const float* stats_part = nullptr, float* stats = nullptr,
+                  int algo = 0, int B = 0, float cp = 0.f, float cv = 0.f,
+                  float ce = 0.f, float creg = 0.f) {
   constexpr int G = 4 * H;
   const bool dual = x2.has_value();
   const int half = dual ? (int)dbody_w.size(1) : H;
@@ -84,22 +104,34 @@ void launch_wgrad(const at::Tensor& x, const at::Tensor& h0,
   // one fused launch, flat grid: gate GEMM tiles (both GEMMs) first, then
   // the small-grad blocks
   const int total_waves = F * half + half + F2 * half2 + half2 + G + H * D + D;
-  dim3 grid(wgrad_flat_grid<H>(total_waves));
+  // + the stats-reduce block of the on-policy row step
+  const int work_blocks = wgrad_flat_grid<H>(total_waves);
+  const int reduce_block = stats_part != nullptr ? work_blocks : -1;
+  dim3 grid(work_blocks + (stats_part != nullptr ? 1 : 0));
   const int tab_lds = N * sizeof(const float*);
   TORCH_CHECK(tab_lds <= 64 * 1024, "wgrad row table exceeds LDS (B*S too big)");
   float* nrm = norm_sq.has_value() ? norm_sq->data_ptr<float>() : nullptr;
-  hipLaunchKernelGGL((wgrad_gates_mfma_kernel<H>), grid, dim3(256), tab_lds,
-                     current_stream(), stash.data_ptr<float>(),
-                     h0.data_ptr<float>(), dgates.data_ptr<float>(),
-                     dw_ih.data_ptr<float>(), dw_hh.data_ptr<float>(), nrm,
-                     x.data_ptr<float>(), dxb.data_ptr<float>(),
-                     gouts.data_ptr<float>(), dbody_w.data_ptr<float>(),
-                     dbody_b.data_ptr<float>(), db_g.data_ptr<float>(),
-                     dheads_w.data_ptr<float>(), dheads_b.data_ptr<float>(),
-                     F, D, N, S, (long)h0.stride(0),
-                     dual ? x2->data_ptr<float>() : nullptr, F2,
-                     dual ? dbody2_w->data_ptr<float>() : nullptr,
-                     dual ? dbody2_b->data_ptr<float>() : nullptr, half);
+  // the instantiation without the reduce block is the plain sweep
+  auto launch = [&](auto reduce) {
+    hipLaunchKernelGGL(
+        (wgrad_gates_mfma_kernel<H, decltype(reduce)::value>), grid,
+        dim3(256), tab_lds, current_stream(), stash.data_ptr<float>(),
+        h0.data_ptr<float>(), dgates.data_ptr<float>(),
+        dw_ih.data_ptr<float>(), dw_hh.data_ptr<float>(), nrm,
+        x.data_ptr<float>(), dxb.data_ptr<float>(), gouts.data_ptr<float>(),
+        dbody_w.data_ptr<float>(), dbody_b.data_ptr<float>(),
+        db_g.data_ptr<float>(), dheads_w.data_ptr<float>(),
+        dheads_b.data_ptr<float>(), F, D, N, S, (long)h0.stride(0),
+        dual ? x2->data_ptr<float>() : nullptr, F2,
+        dual ? dbody2_w->data_ptr<float>() : nullptr,
+        dual ? dbody2_b->data_ptr<float>() : nullptr, half, reduce_block,
+        stats_part, stats, algo, B, cp, cv, ce, creg);
+  };
+  if (stats_part != nullptr) {
+    launch(std::true_type{});
+  } else {
+    launch(std::false_type{});
+  }
   HIP_CHECK_LAST();
 }
 
@@ -154,7 +186,11 @@ void seq_lstm_wgrad_out_hip(const at::Tensor& x, const at::Tensor& h0,
                             const c10::optional<at::Tensor>& norm_sq,
                             const c10::optional<at::Tensor>& x2,
                             const c10::optional<at::Tensor>& dbody2_w_opt,
-                            const c10::optional<at::Tensor>& dbody2_b_opt) {
+                            const c10::optional<at::Tensor>& dbody2_b_opt,
+                            const c10::optional<at::Tensor>& stats_part,
+                            const c10::optional<at::Tensor>& stats, long algo,
+                            long B_stats, double cp, double cv, double ce,
+                            double creg) {
   CHECK_IN(x); CHECK_IN(stash); CHECK_IN(dgates);
   CHECK_IN(dxb); CHECK_IN(gouts);
   CHECK_GPU(h0); CHECK_F32(h0);
@@ -170,12 +206,32 @@ void seq_lstm_wgrad_out_hip(const at::Tensor& x, const at::Tensor& h0,
     dbw2p = &dbw2;
     dbb2p = &dbb2;
   }
+  // optional: reduce the on-policy per-row loss partials in one extra block
+  const float* sp = nullptr;
+  float* st = nullptr;
+  if (stats_part.has_value()) {
+    TORCH_CHECK(stats.has_value(), "stats_part needs the stats vector");
+    CHECK_IN((*stats_part)); CHECK_IN((*stats));
+    TORCH_CHECK(algo >= kAlgoImpala && algo <= kAlgoPpoC,
+                "the stats reduce covers IMPALA / PPO / PPO-C");
+    TORCH_CHECK(B_stats == B && S >= 2 && D >= 2 &&
+                    stats_part->numel() >= (long)B * 8 &&
+                    stats->numel() >= 7,
+                "wgrad_out: stats operands do not match (B, S, D)");
+    sp = stats_part->data_ptr<float>();
+    st = stats->data_ptr<float>();
+  }
+#define PDRL_WG_ARGS                                                         \
+  x, h0, stash, dgates, dxb, gouts, dw_ih, dw_hh, dbody_w, dbody_b, db_g,    \
+      dheads_w, dheads_b, norm_sq, N, S, F, D, x2, dbw2p, dbb2p, sp, st,     \
+      (int)algo, B, (float)cp, (float)cv, (float)ce, (float)creg
   switch (H) {
-    case 32: launch_wgrad<32>(x, h0, stash, dgates, dxb, gouts, dw_ih, dw_hh, dbody_w, dbody_b, db_g, dheads_w, dheads_b, norm_sq, N, S, F, D, x2, dbw2p, dbb2p); break;
-    case 64: launch_wgrad<64>(x, h0, stash, dgates, dxb, gouts, dw_ih, dw_hh, dbody_w, dbody_b, db_g, dheads_w, dheads_b, norm_sq, N, S, F, D, x2, dbw2p, dbb2p); break;
-    case 128: launch_wgrad<128>(x, h0, stash, dgates, dxb, gouts, dw_ih, dw_hh, dbody_w, dbody_b, db_g, dheads_w, dheads_b, norm_sq, N, S, F, D, x2, dbw2p, dbb2p); break;
+    case 32: launch_wgrad<32>(PDRL_WG_ARGS); break;
+    case 64: launch_wgrad<64>(PDRL_WG_ARGS); break;
+    case 128: launch_wgrad<128>(PDRL_WG_ARGS); break;
     default: TORCH_CHECK(false, "hidden size ", H, " unsupported");
   }
+#undef PDRL_WG_ARGS
 }
 
 std::vector<at::Tensor> seq_lstm_wgrad_hip(
@@ -200,7 +256,8 @@ std::vector<at::Tensor> seq_lstm_wgrad_hip(
   }
   seq_lstm_wgrad_out_hip(x, h0, stash, dgates, dxb, gouts, dw_ih, dw_hh,
                          dbody_w, dbody_b, db_g, dheads_w, dheads_b,
-                         c10::nullopt, x2, dbw2, dbb2);
+                         c10::nullopt, x2, dbw2, dbb2, c10::nullopt,
+                         c10::nullopt, 0, 0, 0., 0., 0., 0.);
   if (dual)
     return {dw_ih, dw_hh, dbody_w, dbody_b, db_g, dheads_w, dheads_b, *dbw2,
             *dbb2};

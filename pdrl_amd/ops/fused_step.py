@@ -3,28 +3,36 @@ as a fixed HIP kernel DAG, bypassing autograd, with optional hipGraph
 capture.
 
 The loss math has ONE implementation — the row-local device functions of
-csrc/loss_row.h (plus V-MPO's cross-row vmpo_mid) — reached by two launch
+csrc/loss_row.h (plus V-MPO's cross-row vmpo_mid) — reached by three launch
 sequences:
 
-Fused rows (H=64, the default; 41 µs/step, profiles/wgrad_latency.md):
-  1. seq_lstm_fwd_loss  — forward + the row's loss phase (V-trace/GAE scans,
-                          analytic head grads, per-row stat partials; for
-                          V-MPO, the log-softmax + GAE pre-phase)
-  2. [vmpo_mid]         — V-MPO only: single-block cross-row kernel
-                          (radix-256 top-half selection, psi softmax,
-                          eta/alpha duals, stats)
-  3. seq_lstm_bwd_fin   — stat-partial reduce (block 0) + BPTT per row;
-                          for V-MPO, the analytic grad emission per row
-  4. seq_lstm_wgrad_out — MFMA weight-grad GEMMs written DIRECTLY into the
-                          flat grad buffer's parameter views
-  5. rmsprop/adam       — fused clip + update
+Row step (H=64, IMPALA / PPO / PPO-C, at most one batch row per CU; the
+default; profiles/row_step.md):
+  1. seq_lstm_row_step  — per batch row, in ONE launch: forward, the row's
+                          loss phase (V-trace/GAE scans, analytic head
+                          grads, per-row stat partials) and BPTT. Nothing
+                          in it crosses rows, so no launch boundary
+  2. seq_lstm_wgrad_out — MFMA weight-grad GEMMs written DIRECTLY into the
+                          flat grad buffer's parameter views; one extra
+                          block reduces the stat partials
+  3. rmsprop/adam       — fused clip + update
      [world > 1: RCCL all-reduce of the flat bucket before the update]
+
+Fused pair (H=64: V-MPO, whose middle kernel IS cross-row; the others with
+more rows than CUs, where the row step measured slower):
+  1. seq_lstm_fwd_loss  — forward + the log-softmax + GAE pre-phase
+  2. vmpo_mid           — single-block cross-row kernel (radix-256 top-half
+                          selection, psi softmax, eta/alpha duals, stats)
+  3. seq_lstm_bwd_fin   — the analytic grad emission + BPTT per row (for
+                          the other algorithms: stat-partial reduce in
+                          block 0 + BPTT; kept as the row step's reference)
+  4-5. seq_lstm_wgrad_out and the optimizer, as above
 
 Separate launches (H=32/128, or PDRL_FWDLOSS=0 at H=64): the same device
 functions behind their own thin launches —
   seq_lstm_forward → onpolicy_loss_rows → onpolicy_stats_fin
   (V-MPO: vmpo_mid → vmpo_grad_rows) → seq_lstm_backward_core
-— then steps 4-5 as above.
+— then the weight-grad and optimizer launches as above.
 
 No host syncs anywhere; stats are read back only at the log interval.
 With hipGraph capture (`use_graph`), the whole step replays as one graph
@@ -52,6 +60,7 @@ BATCH_FIELDS = ["obs", "act", "rew", "logits", "log_prob", "is_fir", "hx", "cx"]
 
 _ALGO_ID = {"IMPALA": 0, "PPO": 1, "PPO-C": 2, "V-MPO": 3}  # csrc/loss_row.h
 _WGRAD_MAX_ROWS = 8192          # row-pointer table of the wgrad kernels (LDS)
+_ROW_STEP_MAX_LDS_BYTES = 64 * 1024  # dynamic LDS of one launch
 _VMPO_MID_LDS_BYTES = 56 * 1024  # vmpo_mid keeps s_adv + s_psi (BT each) in LDS
 
 
@@ -119,6 +128,7 @@ class GraphableStep:
 
 class FusedOnPolicyStep(GraphableStep):
     _ws_shape = None
+    _n_cus = None
     _split_graphs = None
     _split_failed = False
 
@@ -144,6 +154,8 @@ class FusedOnPolicyStep(GraphableStep):
         # PDRL_FWDLOSS=0 selects the separate launches there too
         self.fused_rows = core.w_ih.size(0) == 64 and bool(
             int(os.environ.get("PDRL_FWDLOSS", "1")))
+        # forward + loss + BPTT in one launch wherever nothing crosses rows
+        self.row_step = self.fused_rows and algo != "V-MPO"
         self.use_graph = use_graph
         self._graph = None
         self._static: dict[str, torch.Tensor] | None = None
@@ -214,9 +226,32 @@ class FusedOnPolicyStep(GraphableStep):
         self._ws, self._ws_shape = ws, (B, S)
         return ws
 
+    def _runs_row_step(self, e, B, S, D) -> bool:
+        """Whether this shape takes the one-launch row step; otherwise the
+        two-launch pair runs (same results, bit for bit).
+        - One block per CU at the most. The row step takes memory round
+          trips off a block's critical path, which pays while every block
+          has a CU to itself; it needs 175 VGPRs (2 blocks per CU, the pair's
+          kernels fit 3), and with several blocks per CU it measured slower
+          than the pair: +8.2 us at B=640, +5.6 us at B=1536. Measured on
+          256 CUs: B=128 gains 4.3 us and B=256, the edge of this gate,
+          3.5 us; no B between 256 and 640 was measured, so the true
+          crossover is unknown (profiles/row_step.md).
+        - It parks its loss inputs in LDS behind the forward's buffers;
+          where that does not fit a launch, the pair still may."""
+        if not self.row_step:
+            return False
+        if self._n_cus is None:
+            self._n_cus = torch.cuda.get_device_properties(
+                self.core.body_w.device).multi_processor_count
+        return (B <= self._n_cus and e.seq_lstm_row_step_lds_bytes(
+            S, D, _ALGO_ID[self.algo]) <= _ROW_STEP_MAX_LDS_BYTES)
+
     def _loss(self, e, batch, ws):
-        """Forward, loss and BPTT for every row: fills ws["gouts"] and the
-        stats vector; returns (stash, dgates, dxb) for the wgrad kernel."""
+        """Forward, loss and BPTT for every row: fills ws["gouts"] and —
+        except on the row step, which leaves the reduce to the wgrad launch
+        — the stats vector. Returns (hx0, stash, dgates, dxb, stats_kw):
+        the wgrad kernel's inputs and its stats-reduce arguments."""
         c, p = self.core, self.params
         x = batch["obs"]
         B, S, _ = x.shape
@@ -243,6 +278,16 @@ class FusedOnPolicyStep(GraphableStep):
                      *coefs[:3], p.eps_clip, coefs[3])
         pre = ({k: ws[k] for k in ("vm_lse", "vm_logp", "vm_adv", "vm_td")}
                if vmpo else {})
+
+        if self._runs_row_step(e, B, S, D):
+            e.seq_lstm_row_step(x, hx0, cx0, *weights, ws["outs"], ws["hS"],
+                                ws["cS"], ws["stash"], act, behav, rew, fir,
+                                gouts, part, norm, ws["dgates"], ws["dxb"],
+                                *loss_args[7:])
+            stats_kw = dict(stats_part=part, stats=self.stats_buf,
+                            algo=algo_i, B=B, cp=coefs[0], cv=coefs[1],
+                            ce=coefs[2], creg=coefs[3])
+            return hx0, ws["stash"], ws["dgates"], ws["dxb"], stats_kw
 
         if self.fused_rows:
             outs, stash = ws["outs"], ws["stash"]
@@ -287,15 +332,16 @@ class FusedOnPolicyStep(GraphableStep):
                                      *coefs)
             _, _, _, dgates, dxb = e.seq_lstm_backward_core(
                 gouts, None, None, stash, x, cx0, *bwd_weights)
-        return hx0, stash, dgates, dxb
+        return hx0, stash, dgates, dxb, {}
 
     def _body(self, batch, update: bool = True):
         e = ext()
         x = batch["obs"]
         ws = self._workspace(x.size(0), x.size(1))
-        hx0, stash, dgates, dxb = self._loss(e, batch, ws)
+        hx0, stash, dgates, dxb, stats_kw = self._loss(e, batch, ws)
         e.seq_lstm_wgrad_out(x, hx0, stash, dgates, dxb, ws["gouts"],
-                             *self._grad_views(), self._norm_buf())
+                             *self._grad_views(), self._norm_buf(),
+                             **stats_kw)
         if not update:
             return
         if self.grad_reducer is not None:
