@@ -39,6 +39,8 @@ void seq_lstm_row_step_hip(
     double, double, double, double, double, double, double, double, double,
     double);
 long seq_lstm_row_step_lds_bytes(long, long, long);
+long seq_lstm_row_step_split_lds_bytes(long, long, long);
+bool seq_lstm_row_step_uses_split(long, long, long);
 void seq_lstm_forward_multi_hip(const at::Tensor&, const at::Tensor&,
                                 const at::Tensor&, const at::Tensor&,
                                 const at::Tensor&, long, long, long, long);
@@ -347,6 +349,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eps_clip"), py::arg("creg"));
   m.def("seq_lstm_row_step_lds_bytes", &seq_lstm_row_step_lds_bytes,
         "dynamic LDS one seq_lstm_row_step block needs (launch limit 64 KiB)",
+        py::arg("S"), py::arg("D"), py::arg("algo"));
+  m.def("seq_lstm_row_step_split_lds_bytes",
+        &seq_lstm_row_step_split_lds_bytes,
+        "dynamic LDS of the row step with the input projections computed "
+        "ahead of the forward's time loop and the head weights in LDS",
+        py::arg("S"), py::arg("D"), py::arg("algo"));
+  m.def("seq_lstm_row_step_uses_split", &seq_lstm_row_step_uses_split,
+        "whether seq_lstm_row_step launches that instantiation (its LDS "
+        "fits a launch)",
         py::arg("S"), py::arg("D"), py::arg("algo"));
   m.def("seq_lstm_bwd_fin", &seq_lstm_bwd_fin_hip,
         "BPTT backward + stat finalization (or V-MPO grad emission)",

@@ -20,8 +20,19 @@ constexpr int kStashFields = 7;
 // reference: networks/models.py MlpLSTMCriticContinuous 273-322). Single
 // body passes half == H and the extra pointers null; body_w's column
 // stride is ``half`` in both modes (== H for single).
-template <int H>
-__device__ __forceinline__ void seq_lstm_fwd_row(
+//
+// kHoist takes what does not depend on h off the serial part of the row:
+// - One pass after the body computes px[t][col] = bias + Σ_k xb[t][k]·
+//   w_ih[k][col] for every step into S·4H more floats of LDS (behind cbuf),
+//   and a step of the recurrence starts its accumulator from px[t] and adds
+//   only the 64 w_hh terms. Each accumulator sees the same fmaf sequence as
+//   without kHoist, so every output keeps its bits.
+// - heads_w and heads_b are requested with the gate weights at the top and
+//   kept in LDS behind px (H·D + D floats), so the heads behind the time
+//   loop issue no global load: a load there comes back only behind every
+//   store the loop has issued.
+template <int H, bool kHoist>
+__device__ __forceinline__ void seq_lstm_fwd_row_on(
     const float* __restrict__ x,       // (B,S,F)
     const float* __restrict__ h0,      // (B,H)
     const float* __restrict__ c0,      // (B,H)
@@ -50,6 +61,15 @@ __device__ __forceinline__ void seq_lstm_fwd_row(
   float* gates = hs + S * H;                       // (4H)
   float* hbuf = gates + G;                         // (H)
   float* cbuf = hbuf + H;                          // (H)
+  float* px = cbuf + H;                            // (S,4H), kHoist only
+  float* hw_s = px + S * G;                        // (H,D),  kHoist only
+  float* hb_s = hw_s + H * D;                      // (D),    kHoist only
+
+  float r_hw = 0.0f, r_hb = 0.0f;
+  if constexpr (kHoist) {
+    if (tid < H * D) r_hw = heads_w[tid];
+    if (tid < D) r_hb = heads_b[tid];
+  }
 
   // Register-resident gate weight columns (thread = gate column tid).
   float wih[H], whh[H];
@@ -60,6 +80,14 @@ __device__ __forceinline__ void seq_lstm_fwd_row(
   PDRL_PIN_REGS(wih, H);
   PDRL_PIN_REGS(whh, H);
   const float bias = b_g[tid];
+  if constexpr (kHoist) {
+    // the wait for the gate weights has covered these two loads; a head
+    // wider than the block (H·D > 4H) fetches the rest here
+    if (tid < H * D) hw_s[tid] = r_hw;
+    if (tid < D) hb_s[tid] = r_hb;
+    for (int i = tid + G; i < H * D; i += G) hw_s[i] = heads_w[i];
+    for (int i = tid + G; i < D; i += G) hb_s[i] = heads_b[i];
+  }
 
   // Body GEMM + ReLU for all S steps of this row (K1); dual mode computes
   // the [obs-enc | act-enc] split in the same pass.
@@ -88,28 +116,66 @@ __device__ __forceinline__ void seq_lstm_fwd_row(
   }
   __syncthreads();
 
+  if constexpr (kHoist) {
+    // Input projection of every step. A step's 16 broadcast reads go out in
+    // one burst ahead of its fmaf chain (the waits count down behind them),
+    // and no step waits for another. Thread tid alone writes and later
+    // reads column tid of px: no bank conflict and no barrier.
+    for (int t = 0; t < S; ++t) {
+      const float4* xbt4 = reinterpret_cast<const float4*>(xb + t * H);
+      float4 xv[H / 4];
+#pragma unroll
+      for (int k = 0; k < H / 4; ++k) xv[k] = xbt4[k];
+      float acc = bias;
+#pragma unroll
+      for (int k = 0; k < H / 4; ++k) {
+        acc = fmaf(xv[k].x, wih[4 * k], acc);
+        acc = fmaf(xv[k].y, wih[4 * k + 1], acc);
+        acc = fmaf(xv[k].z, wih[4 * k + 2], acc);
+        acc = fmaf(xv[k].w, wih[4 * k + 3], acc);
+      }
+      px[t * G + tid] = acc;
+    }
+  }
+
   // LSTM recurrence, whole sequence in-kernel (K2).
   for (int t = 0; t < S; ++t) {
     // vectorized LDS broadcast reads: ds_read_b128 moves 4 floats per
     // 4 cycles vs 4× ds_read_b32 at 2 cycles each (§LDS table)
-    const float4* xbt4 = reinterpret_cast<const float4*>(xb + t * H);
     const float4* h4 = reinterpret_cast<const float4*>(hbuf);
-    float acc = bias;
+    float acc;
+    if constexpr (kHoist) {
+      // px[t] and h are requested together before the first fmaf
+      acc = px[t * G + tid];
+      float4 hv[H / 4];
 #pragma unroll
-    for (int k = 0; k < H / 4; ++k) {
-      const float4 xv = xbt4[k];
-      acc = fmaf(xv.x, wih[4 * k], acc);
-      acc = fmaf(xv.y, wih[4 * k + 1], acc);
-      acc = fmaf(xv.z, wih[4 * k + 2], acc);
-      acc = fmaf(xv.w, wih[4 * k + 3], acc);
-    }
+      for (int k = 0; k < H / 4; ++k) hv[k] = h4[k];
 #pragma unroll
-    for (int k = 0; k < H / 4; ++k) {
-      const float4 hv = h4[k];
-      acc = fmaf(hv.x, whh[4 * k], acc);
-      acc = fmaf(hv.y, whh[4 * k + 1], acc);
-      acc = fmaf(hv.z, whh[4 * k + 2], acc);
-      acc = fmaf(hv.w, whh[4 * k + 3], acc);
+      for (int k = 0; k < H / 4; ++k) {
+        acc = fmaf(hv[k].x, whh[4 * k], acc);
+        acc = fmaf(hv[k].y, whh[4 * k + 1], acc);
+        acc = fmaf(hv[k].z, whh[4 * k + 2], acc);
+        acc = fmaf(hv[k].w, whh[4 * k + 3], acc);
+      }
+    } else {
+      const float4* xbt4 = reinterpret_cast<const float4*>(xb + t * H);
+      acc = bias;
+#pragma unroll
+      for (int k = 0; k < H / 4; ++k) {
+        const float4 xv = xbt4[k];
+        acc = fmaf(xv.x, wih[4 * k], acc);
+        acc = fmaf(xv.y, wih[4 * k + 1], acc);
+        acc = fmaf(xv.z, wih[4 * k + 2], acc);
+        acc = fmaf(xv.w, wih[4 * k + 3], acc);
+      }
+#pragma unroll
+      for (int k = 0; k < H / 4; ++k) {
+        const float4 hv = h4[k];
+        acc = fmaf(hv.x, whh[4 * k], acc);
+        acc = fmaf(hv.y, whh[4 * k + 1], acc);
+        acc = fmaf(hv.z, whh[4 * k + 2], acc);
+        acc = fmaf(hv.w, whh[4 * k + 3], acc);
+      }
     }
     const int sel = tid / H;  // 0:i 1:f 2:g 3:o
     const float a = (sel == 2) ? tanhf(acc) : sigmoidf_dev(acc);
@@ -136,21 +202,52 @@ __device__ __forceinline__ void seq_lstm_fwd_row(
   }
 
   // Heads (K3) on the stored h sequence (LDS reads vectorized).
+  const float* hw = kHoist ? hw_s : heads_w;
+  const float* hb = kHoist ? hb_s : heads_b;
   for (int idx = tid; idx < S * D; idx += G) {
     const int t = idx / D, d = idx % D;
-    float acc = heads_b[d];
+    float acc = hb[d];
     const float4* ht4 = reinterpret_cast<const float4*>(hs + t * H);
 #pragma unroll
     for (int k = 0; k < H / 4; ++k) {
       const float4 hv = ht4[k];
-      acc = fmaf(hv.x, heads_w[(4 * k) * D + d], acc);
-      acc = fmaf(hv.y, heads_w[(4 * k + 1) * D + d], acc);
-      acc = fmaf(hv.z, heads_w[(4 * k + 2) * D + d], acc);
-      acc = fmaf(hv.w, heads_w[(4 * k + 3) * D + d], acc);
+      acc = fmaf(hv.x, hw[(4 * k) * D + d], acc);
+      acc = fmaf(hv.y, hw[(4 * k + 1) * D + d], acc);
+      acc = fmaf(hv.z, hw[(4 * k + 2) * D + d], acc);
+      acc = fmaf(hv.w, hw[(4 * k + 3) * D + d], acc);
     }
     outs[((long)b * S + t) * D + d] = acc;
     if (outs_lds != nullptr) outs_lds[idx] = acc;
   }
+}
+
+// Input projection inside the time loop: (2·S·H + 6·H) floats of LDS.
+template <int H>
+__device__ __forceinline__ void seq_lstm_fwd_row(
+    const float* __restrict__ x,       // (B,S,F)
+    const float* __restrict__ h0,      // (B,H)
+    const float* __restrict__ c0,      // (B,H)
+    const float* __restrict__ body_w,  // (F,H)
+    const float* __restrict__ body_b,  // (H)
+    const float* __restrict__ w_ih,    // (H,4H)
+    const float* __restrict__ w_hh,    // (H,4H)
+    const float* __restrict__ b_g,     // (4H)
+    const float* __restrict__ heads_w, // (H,D)
+    const float* __restrict__ heads_b, // (D)
+    float* __restrict__ outs,          // (B,S,D)
+    float* __restrict__ hS,            // (B,H)
+    float* __restrict__ cS,            // (B,H)
+    float* __restrict__ stash,         // (B,S,7H)
+    int b, int S, int F, int D, long h0s, char* smem_raw,
+    const float* __restrict__ x2 = nullptr,       // (B,S,F2) dual body
+    const float* __restrict__ body2_w = nullptr,  // (F2,half)
+    const float* __restrict__ body2_b = nullptr,  // (half)
+    int F2 = 0, int half = H,
+    float* outs_lds = nullptr) {  // (S,D) LDS copy of this row's outs
+  seq_lstm_fwd_row_on<H, false>(x, h0, c0, body_w, body_b, w_ih, w_hh, b_g,
+                                heads_w, heads_b, outs, hS, cS, stash, b, S,
+                                F, D, h0s, smem_raw, x2, body2_w, body2_b, F2,
+                                half, outs_lds);
 }
 
 

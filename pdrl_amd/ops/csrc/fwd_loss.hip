@@ -146,6 +146,12 @@ constexpr long kRowStepMaxLds = 64 * 1024;  // dynamic LDS of a launch
 __host__ __device__ constexpr int fwd_row_lds_floats(int S, int H) {
   return 2 * S * H + 4 * H + 2 * H;
 }
+// The same with what seq_lstm_fwd_row_on<H, true> keeps behind them: the
+// hoisted input projections px (S,4H) and the head weights (H,D), (D).
+__host__ __device__ constexpr int fwd_row_split_lds_floats(int S, int H,
+                                                           int D) {
+  return fwd_row_lds_floats(S, H) + 4 * S * H + H * D + D;
+}
 
 // The whole row-local step of IMPALA / PPO / PPO-C in ONE launch: block b
 // forwards its row, runs the row's loss phase and back-propagates through
@@ -160,7 +166,12 @@ __host__ __device__ constexpr int fwd_row_lds_floats(int S, int H) {
 // top (their latency sits under the forward) and parked in LDS behind the
 // forward's buffers, where the heads also leave a copy of the outs they
 // store. BPTT's LDS overlays all of it once the loss phase is done.
-template <int H>
+//
+// kSplit runs the forward with the input projection x·w_ih of all steps
+// computed ahead of its time loop and the head weights kept in LDS
+// (seq_lstm_fwd_row_on<H, true>). Same bits, more LDS; the launcher takes
+// kSplit where that LDS fits a launch.
+template <int H, bool kSplit>
 __global__ __launch_bounds__(4 * H) void seq_lstm_row_step_kernel(
     const float* __restrict__ x, const float* __restrict__ h0,
     const float* __restrict__ c0, const float* __restrict__ body_w,
@@ -183,7 +194,9 @@ __global__ __launch_bounds__(4 * H) void seq_lstm_row_step_kernel(
   const long sb = (long)b * S;
   const int act_per = (algo == kAlgoPpoC) ? (D - 1) / 2 : 1;
   float* s_outs =
-      reinterpret_cast<float*>(smem_raw) + fwd_row_lds_floats(S, H);  // (S,D)
+      reinterpret_cast<float*>(smem_raw) +
+      (kSplit ? fwd_row_split_lds_floats(S, H, D)
+              : fwd_row_lds_floats(S, H));                      // (S,D)
   float* s_act = s_outs + S * D;                                // (S,act_per)
   float* s_behav = s_act + S * act_per;                         // (S)
   float* s_rew = s_behav + S;                                   // (S)
@@ -199,9 +212,10 @@ __global__ __launch_bounds__(4 * H) void seq_lstm_row_step_kernel(
     r_rew = rew[sb + tid];
     r_fir = fir[sb + tid];
   }
-  seq_lstm_fwd_row<H>(x, h0, c0, body_w, body_b, w_ih, w_hh, b_g, heads_w,
-                      heads_b, outs, hS, cS, stash, b, S, F, D, h0s,
-                      smem_raw, nullptr, nullptr, nullptr, 0, H, s_outs);
+  seq_lstm_fwd_row_on<H, kSplit>(x, h0, c0, body_w, body_b, w_ih, w_hh, b_g,
+                                 heads_w, heads_b, outs, hS, cS, stash, b, S,
+                                 F, D, h0s, smem_raw, nullptr, nullptr,
+                                 nullptr, 0, H, s_outs);
   if (tid < S) {
     if (algo != kAlgoPpoC) s_act[tid] = r_act;
     s_behav[tid] = r_behav;
@@ -249,6 +263,25 @@ long seq_lstm_row_step_lds_bytes(long S, long D, long algo) {
   const long lds_loss = 6 * S;
   const long lds_bwd = S * H + G + S * H + 2 * G;
   return std::max(std::max(lds_fwd, lds_loss), lds_bwd) * (long)sizeof(float);
+}
+
+// The same for the split instantiation, whose forward keeps px (S,4H) and
+// the head weights as well; the loss phase and BPTT are the same.
+long seq_lstm_row_step_split_lds_bytes(long S, long D, long algo) {
+  constexpr long H = 64, G = 4 * H;
+  const long act_per = (algo == kAlgoPpoC) ? (D - 1) / 2 : 1;
+  const long lds_fwd = fwd_row_split_lds_floats((int)S, (int)H, (int)D) +
+                       S * D + S * act_per + 3 * S;
+  const long lds_loss = 6 * S;
+  const long lds_bwd = S * H + G + S * H + 2 * G;
+  return std::max(std::max(lds_fwd, lds_loss), lds_bwd) * (long)sizeof(float);
+}
+
+// Whether seq_lstm_row_step launches the split instantiation for this shape:
+// wherever its LDS fits a launch. The other instantiation's need is never
+// larger, so no shape loses the row step to this.
+bool seq_lstm_row_step_uses_split(long S, long D, long algo) {
+  return seq_lstm_row_step_split_lds_bytes(S, D, algo) <= kRowStepMaxLds;
 }
 
 // Forward + loss + BPTT per row for IMPALA / PPO / PPO-C (V-MPO's middle
@@ -306,13 +339,17 @@ void seq_lstm_row_step_hip(
                   stats_part.numel() >= (long)B * 8,
               "row_step: operand shapes do not match x");
   constexpr int G = 4 * 64;
-  const long lds = seq_lstm_row_step_lds_bytes(S, D, algo);
+  const bool split = seq_lstm_row_step_uses_split(S, D, algo);
+  const long lds = split ? seq_lstm_row_step_split_lds_bytes(S, D, algo)
+                         : seq_lstm_row_step_lds_bytes(S, D, algo);
   TORCH_CHECK(lds <= kRowStepMaxLds, "row_step needs ", lds,
               " bytes of LDS for (S, D) = (", S, ", ", D,
               "); run seq_lstm_fwd_loss + seq_lstm_bwd_fin instead");
+  const auto kernel = split ? seq_lstm_row_step_kernel<64, true>
+                            : seq_lstm_row_step_kernel<64, false>;
   hipLaunchKernelGGL(
-      (seq_lstm_row_step_kernel<64>), dim3(B), dim3(G), lds,
-      current_stream(), x.data_ptr<float>(), h0.data_ptr<float>(),
+      kernel, dim3(B), dim3(G), lds, current_stream(), x.data_ptr<float>(),
+      h0.data_ptr<float>(),
       c0.data_ptr<float>(), body_w.data_ptr<float>(),
       body_b.data_ptr<float>(), w_ih.data_ptr<float>(),
       w_hh.data_ptr<float>(), b_g.data_ptr<float>(),

@@ -231,7 +231,7 @@ class FusedOnPolicyStep(GraphableStep):
         two-launch pair runs (same results, bit for bit).
         - One block per CU at the most. The row step takes memory round
           trips off a block's critical path, which pays while every block
-          has a CU to itself; it needs 175 VGPRs (2 blocks per CU, the pair's
+          has a CU to itself; it needs 175-207 VGPRs (2 blocks/CU, the pair's
           kernels fit 3), and with several blocks per CU it measured slower
           than the pair: +8.2 us at B=640, +5.6 us at B=1536. Measured on
           256 CUs: B=128 gains 4.3 us and B=256, the edge of this gate,
