@@ -1,26 +1,41 @@
-// Device actor: fused policy-act + env-step rollout for CDNA4 (gfx950).
+// Device actor: fused policy-act + env-step kernels for CDNA4 (gfx950).
 //
-// One launch advances N native environments by S steps and writes the
-// (N, S, ·) batch in the learner's own field layout (buffers.rollout_fields)
-// straight into persistent device tensors: policy forward, categorical
-// sample, log-prob, env dynamics, termination and auto-reset never leave the
-// GPU. The single-call CPU counterpart is cpu_actor.cpp::act_batch_discrete;
-// the eager oracle is pdrl_amd/ops/rollout.py. rollout_gaussian (below) is the
-// continuous-control sibling: same geometry and recurrent part, a Gaussian
-// policy (PPO-C / SAC-C sampling schemes of cpu_actor.cpp::act_batch_gaussian)
-// and a float action. rollout_eval_discrete / rollout_eval_gaussian (further
-// below) are the greedy evaluation kernels: whole episodes, no batch.
+// Two kernels, each composed from a policy scheme and shared helpers:
+//
+//   rollout_train<H, Policy>  one launch advances N native environments by S
+//     steps and writes the (N, S, ·) batch in the learner's own field layout
+//     (buffers.rollout_fields) straight into persistent device tensors:
+//     policy forward, sample, log-prob, env dynamics, termination and
+//     auto-reset never leave the GPU. Per-env state is carried from launch to
+//     launch. Bindings rollout_discrete and rollout_gaussian.
+//   rollout_eval<H, Policy>   greedy evaluation: E whole episodes per env
+//     under the deterministic action, one return and one length per (env,
+//     episode), no batch, nothing persistent. Bindings rollout_eval_discrete
+//     and rollout_eval_gaussian.
+//
+// The eager oracles are pdrl_amd/ops/rollout.py and pdrl_amd/ops/evaluate.py,
+// the single-call CPU counterparts cpu_actor.cpp::act_batch_discrete /
+// act_batch_gaussian.
 //
 // Geometry: as seq_lstm_fwd_row (core_rows.h) — one 4H-thread workgroup per
 // environment, thread = gate column with its w_ih / w_hh column resident in
-// 2×H VGPRs, loaded once per launch and amortised over the S steps. The
-// environments are independent, so there is no inter-workgroup traffic and
-// no atomics: episode returns are written per (env, step) and reduced
-// lazily by the host. obs, xb, h, c, gates and the logits head columns live
-// in LDS (a few KB). The logits are a wave-0 butterfly reduction; thread 0
-// then samples while wave 1 steps the dynamics for every action (lane =
-// action) and draws the reset uniforms, so the two scalar chains overlap.
-// Five barriers a step.
+// 2×H VGPRs (RecurrentCore), loaded once per launch and amortised over the
+// steps. The environments are independent, so there is no inter-workgroup
+// traffic and no atomics: episode returns are written per (env, step) and
+// reduced lazily by the host. obs, xb, h, c, gates and the head columns live
+// in LDS (a few KB). A step is five barriers: three in RecurrentCore, then
+// wave 0 butterfly-reduces the head columns (reduce_heads) while wave 1 does
+// the scheme's side work (env dynamics that need no action, random draws),
+// thread 0 does the part of the scheme that needs the heads only, barrier,
+// thread 0 finishes the step (action → next state, reward, terminated) and
+// the kernel's episode bookkeeping, barrier.
+//
+// Where things go (two places each, no kernel is touched):
+//   a new env     its traits struct, and its line in the env table of its
+//                 family right below it ("native env dynamics");
+//   a new policy  one scheme struct in "policy schemes" (sampling schemes
+//                 feed rollout_train, greedy ones rollout_eval), and the
+//                 entry point that launches it.
 //
 // Random numbers come from the stateless counter hash in rollout_rng.h,
 // keyed by (seed, env, tick, lane): per-env tick counters live on device and
@@ -31,6 +46,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
 namespace {
 
@@ -39,14 +55,21 @@ namespace {
 constexpr float kNoEpisode = -1.0e30f;
 
 // ---- native env dynamics -------------------------------------------------
-// An env is a traits struct: kObsDim, kActions, reset(state, u[4]) and
-// step(state, action, reward, terminated). A second env is one more struct
-// and one more case in rollout_discrete_hip.
+// An env is a traits struct. Common to both families: kObsDim, kResetDraws
+// (hash lanes 1..kResetDraws feed reset) and reset(state, u[kResetDraws]).
+// The step differs by action type, and the two forms are not put behind one
+// shape: a discrete env has kActions and step(state, action, reward,
+// terminated), cheap enough that wave 1 steps EVERY action while the logits
+// are reduced; a continuous env (further below) cannot enumerate its actions
+// and splits the update at the action instead. A second env is one more
+// struct and one more line in its family's table (with_discrete_env /
+// with_continuous_env).
 
 // CartPole-v1: constants and Euler update of pdrl_amd/envs/cartpole.py, fp32.
 struct CartPoleDyn {
   static constexpr int kObsDim = 4;
   static constexpr int kActions = 2;
+  static constexpr int kResetDraws = 4;
 
   __device__ static void reset(float* s, const float* u) {
     // explicit mul-then-add (no fma contraction): bit-exact vs the oracle
@@ -82,12 +105,10 @@ struct CartPoleDyn {
   }
 };
 
-// Continuous-action envs have their own traits interface: kObsDim, kActDim,
-// kResetDraws (hash lanes 1..kResetDraws feed reset), drift(state) — the part
-// of the update that does not depend on the action, so another wave can
-// evaluate it while the policy heads are still being reduced — and
-// step(state, action, drift, reward, terminated) with a float action. Only
-// the sampled action is stepped (there is no "every action" to enumerate).
+// Continuous-action envs: kActDim, drift(state) — the part of the update
+// that does not depend on the action, so another wave can evaluate it while
+// the policy heads are still being reduced — and step(state, action, drift,
+// reward, terminated) with a float action. Only the chosen action is stepped.
 
 // MountainCarContinuous-v0: constants and update of
 // pdrl_amd/envs/mountain_car.py, fp32, in the op order of the oracle
@@ -123,6 +144,27 @@ struct MountainCarContDyn {
     s[1] = vel;
   }
 };
+
+// Env tables (ids are assigned in pdrl_amd/ops/rollout.py): f(traits, message
+// raised when the core's obs_dim does not match).
+template <typename Fn>
+void with_discrete_env(long env_id, Fn&& f) {
+  switch (env_id) {
+    case 0: f(CartPoleDyn{}, "CartPole needs obs_dim 4"); break;
+    default: TORCH_CHECK(false, "rollout: unknown device env id ", env_id);
+  }
+}
+
+template <typename Fn>
+void with_continuous_env(long env_id, Fn&& f) {
+  switch (env_id) {
+    case 1:
+      f(MountainCarContDyn{}, "MountainCarContinuous needs obs_dim 2");
+      break;
+    default:
+      TORCH_CHECK(false, "rollout: unknown continuous device env id ", env_id);
+  }
+}
 
 // Live policy weights (transposed layout, read by pointer every launch):
 // what the training rollouts and the evaluation kernels have in common.
@@ -160,7 +202,7 @@ struct RolloutArgs : PolicyWeights {
   int time_horizon, max_episode_steps;
 };
 
-// ---- recurrent part, shared by rollout_discrete and rollout_gaussian ------
+// ---- recurrent part, shared by rollout_train and rollout_eval -------------
 // Thread tid of the 4H-thread workgroup owns gate column tid (and, for
 // tid < H, body column tid). load() runs once per launch, step() once per env
 // step; everything is force-inlined so the weight columns stay in the calling
@@ -301,174 +343,7 @@ struct RecurrentCore {
   }
 };
 
-template <int H, typename Env>
-__global__ __launch_bounds__(4 * H) void rollout_discrete(RolloutArgs p) {
-  constexpr int G = 4 * H;
-  constexpr int F = Env::kObsDim;
-  constexpr int A = Env::kActions;
-  const int tid = threadIdx.x;
-  const int n = blockIdx.x;
-  if (n >= p.N) return;  // uniform per workgroup
-
-  __shared__ __attribute__((aligned(16))) float s_xb[H];
-  __shared__ __attribute__((aligned(16))) float s_h[H];
-  __shared__ __attribute__((aligned(16))) float s_c[H];
-  __shared__ __attribute__((aligned(16))) float s_gates[G];
-  __shared__ float s_hw[A * H];  // logits head columns, [a][k]
-  __shared__ float s_obs[F];
-  __shared__ float s_cand[A * F];  // next state for every action
-  __shared__ float s_crew[A];
-  __shared__ int s_cterm[A];
-  __shared__ float s_ur[4];  // reset uniforms of this tick
-  __shared__ float s_fir;
-  __shared__ int s_reset;
-
-  RecurrentCore<H, F> core;
-  core.load(p, tid, n, s_h, s_c);
-  float hb[A];
-#pragma unroll
-  for (int a = 0; a < A; ++a) hb[a] = p.heads_b[a];
-
-  for (int idx = tid; idx < A * H; idx += G) {
-    const int a = idx / H, k = idx % H;
-    s_hw[idx] = p.heads_w[k * p.D + a];
-  }
-  if (tid < F) s_obs[tid] = p.env_state[(long)n * F + tid];
-
-  // episode bookkeeping lives in thread 0's registers across the S steps
-  int steps = 0;
-  float run = 0.0f;
-  unsigned tick = p.tick[n];  // every thread tracks it (hash counter)
-  if (tid == 0) {
-    s_fir = p.is_fir[n];
-    steps = p.ep_steps[n];
-    run = p.ep_run[n];
-  }
-  __syncthreads();
-
-  for (int t = 0; t < p.S; ++t) {
-    const long row = (long)n * p.S + t;
-    tick += 1u;
-    // record the pre-step obs / hx / cx / is_fir; body, gates, cell update
-    core.step(p, tid, row, s_obs, &s_fir, s_xb, s_h, s_c, s_gates);
-
-    // logits = head columns [0, A): wave 0 splits the H-long dot products
-    // over its lanes and butterfly-reduces them (a serial loop in one lane
-    // is ~H dependent LDS round trips — it dominated the step)
-    float lg[A];
-    if (tid < kWave) {
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        float part = 0.0f;
-        for (int k = tid; k < H; k += kWave)
-          part = fmaf(s_h[k], s_hw[a * H + k], part);
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1)
-          part += __shfl_xor(part, off, kWave);
-        lg[a] = part + hb[a];
-      }
-    } else if (tid < kWave + A) {
-      // meanwhile wave 1 steps the dynamics for EVERY action (lane = action)
-      // and draws the reset uniforms: the two single-lane scalar chains
-      // (softmax/sample/log-prob vs sin/cos/divides) run side by side
-      const int a = tid - kWave;
-      float st[F];
-#pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
-      float reward;
-      bool terminated;
-      Env::step(st, a, reward, terminated);
-#pragma unroll
-      for (int k = 0; k < F; ++k) s_cand[a * F + k] = st[k];
-      s_crew[a] = reward;
-      s_cterm[a] = terminated ? 1 : 0;
-    } else if (tid < kWave + A + 4) {
-      const unsigned k = (unsigned)(tid - kWave - A);
-      s_ur[k] = pdrl_rng::uniform(p.seed, (unsigned)n, tick, k + 1u);
-    }
-
-    // softmax, sample, log-prob (thread 0, no barrier needed: it already
-    // holds the reduced logits)
-    int chosen = A - 1;
-    if (tid == 0) {
-      float mx = lg[0];
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        p.logits[row * A + a] = lg[a];
-        mx = fmaxf(mx, lg[a]);
-      }
-      float prob[A];
-      float Z = 0.0f;
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        prob[a] = expf(lg[a] - mx);
-        Z += prob[a];
-      }
-      // inverse CDF against one uniform (rule of cpu_actor.cpp)
-      const float u = pdrl_rng::uniform(p.seed, (unsigned)n, tick, 0u);
-      float cdf = 0.0f;
-      bool found = false;
-      float lg_chosen = lg[A - 1];
-#pragma unroll
-      for (int a = 0; a < A; ++a) {  // static indices: lg/prob stay in VGPRs
-        cdf += prob[a] / Z;
-        if (!found && u < cdf) {
-          chosen = a;
-          lg_chosen = lg[a];
-          found = true;
-        }
-      }
-      p.act[row] = (float)chosen;
-      p.log_prob[row] = lg_chosen - mx - logf(Z);
-    }
-    __syncthreads();
-
-    // pick the sampled action's outcome; termination, auto-reset (thread 0)
-    if (tid == 0) {
-      float st[F];
-#pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = s_cand[chosen * F + k];
-      const float reward = s_crew[chosen];
-      const bool terminated = s_cterm[chosen] != 0;
-      steps += 1;
-      run += reward;
-      p.rew[row] = reward;
-      const bool done = terminated || steps >= p.max_episode_steps;
-      const bool reset = done || steps >= p.time_horizon;
-      p.ep_ret[row] = reset ? run : kNoEpisode;
-      if (reset) {
-        Env::reset(st, s_ur);
-        steps = 0;
-        run = 0.0f;
-      }
-#pragma unroll
-      for (int k = 0; k < F; ++k) s_obs[k] = st[k];
-      s_fir = reset ? 1.0f : 0.0f;
-      s_reset = reset ? 1 : 0;
-    }
-    __syncthreads();
-    // thread j is the only reader of s_h[j] / s_c[j] before the next barrier
-    if (s_reset != 0 && tid < H) {
-      s_h[tid] = 0.0f;
-      s_c[tid] = 0.0f;
-    }
-  }
-
-  // persist the per-env state for the next launch
-  if (tid < H) {
-    p.h[(long)n * H + tid] = s_h[tid];
-    p.c[(long)n * H + tid] = s_c[tid];
-  }
-  if (tid < F) p.env_state[(long)n * F + tid] = s_obs[tid];
-  if (tid == 0) {
-    p.is_fir[n] = s_fir;
-    p.ep_steps[n] = steps;
-    p.ep_run[n] = run;
-    p.tick[n] = tick;
-  }
-}
-
-// ---- Gaussian policy (continuous control) ---------------------------------
+// Arguments of the sampling Gaussian schemes.
 struct GaussianArgs : RolloutArgs {
   float* ou_state;        // (N) persistent OU exploration state (Mode 1)
   int ou_envs;            // envs [0, ou_envs) explore with OU noise forever
@@ -476,221 +351,7 @@ struct GaussianArgs : RolloutArgs {
   float ou_theta, ou_sigma;
 };
 
-// Heads: column 0 = mu, column 1 = std (Mode 0, PPO-C) or log_std (Mode 1,
-// SAC-C); the ``logits`` field is [mu_raw | second_raw], ``act`` has width 1.
-// Per step, after the shared recurrent part: wave 0 butterfly-reduces the two
-// head columns while, in wave 1, one lane turns hash lanes 5 / 6 into the
-// step's standard normal (log / sqrt / cos), one evaluates the env's
-// action-independent drift and kResetDraws lanes draw the reset uniforms.
-// Thread 0 does the part of the scheme's transform that needs the heads only
-// before the barrier too, and after it the sample, the log-prob, the env
-// step, the bookkeeping and the reset. Five barriers a step, as in
-// rollout_discrete. The sampling chain uses the precise libm forms: parity
-// of the sample against the oracle is what the tests measure.
-template <int H, typename Env, int Mode>
-__global__ __launch_bounds__(4 * H) void rollout_gaussian(GaussianArgs p) {
-  // One tick has eight hash lanes: 1..4 reset, 5 / 6 the normal. A second
-  // action dimension needs a wider counter (rollout_rng.h).
-  static_assert(Env::kActDim == 1,
-                "eight hash lanes per tick allow exactly one action dimension");
-  static_assert(Env::kResetDraws >= 1 && Env::kResetDraws <= 4,
-                "reset draws use hash lanes 1..4");
-  static_assert(Mode == 0 || Mode == 1, "Mode: 0 = PPO-C, 1 = SAC-C");
-  constexpr int G = 4 * H;
-  constexpr int F = Env::kObsDim;
-  constexpr int R = Env::kResetDraws;
-  constexpr float kHalfLog2Pi = 0.9189385f;
-  const int tid = threadIdx.x;
-  const int n = blockIdx.x;
-  if (n >= p.N) return;  // uniform per workgroup
-
-  __shared__ __attribute__((aligned(16))) float s_xb[H];
-  __shared__ __attribute__((aligned(16))) float s_h[H];
-  __shared__ __attribute__((aligned(16))) float s_c[H];
-  __shared__ __attribute__((aligned(16))) float s_gates[G];
-  __shared__ float s_hw[2 * H];  // mu and std / log_std head columns, [a][k]
-  __shared__ float s_obs[F];
-  __shared__ float s_ur[R];  // reset uniforms of this tick
-  __shared__ float s_normal;
-  __shared__ float s_drift;
-  __shared__ float s_fir;
-  __shared__ int s_reset;
-
-  RecurrentCore<H, F> core;
-  core.load(p, tid, n, s_h, s_c);
-  float hb[2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a) hb[a] = p.heads_b[a];
-
-  for (int idx = tid; idx < 2 * H; idx += G) {
-    const int a = idx / H, k = idx % H;
-    s_hw[idx] = p.heads_w[k * p.D + a];
-  }
-  if (tid < F) s_obs[tid] = p.env_state[(long)n * F + tid];
-
-  // episode bookkeeping and the OU state live in thread 0's registers
-  int steps = 0;
-  float run = 0.0f, ou = 0.0f;
-  unsigned tick = p.tick[n];  // every thread tracks it (hash counter)
-  if (tid == 0) {
-    s_fir = p.is_fir[n];
-    steps = p.ep_steps[n];
-    run = p.ep_run[n];
-    if constexpr (Mode == 1) ou = p.ou_state[n];
-  }
-  __syncthreads();
-
-  for (int t = 0; t < p.S; ++t) {
-    const long row = (long)n * p.S + t;
-    tick += 1u;
-    core.step(p, tid, row, s_obs, &s_fir, s_xb, s_h, s_c, s_gates);
-
-    float lg[2];
-    if (tid < kWave) {
-      // the two head columns: wave 0 splits the H-long dot products over its
-      // lanes and butterfly-reduces them
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        float part = 0.0f;
-        for (int k = tid; k < H; k += kWave)
-          part = fmaf(s_h[k], s_hw[a * H + k], part);
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1)
-          part += __shfl_xor(part, off, kWave);
-        lg[a] = part + hb[a];
-      }
-    } else if (tid == kWave) {
-      // meanwhile, Box-Muller on hash lanes 5 (radius) and 6 (angle);
-      // 1 - u5 is exact in fp32 and never 0
-      const float u5 = pdrl_rng::uniform(p.seed, (unsigned)n, tick, 5u);
-      const float u6 = pdrl_rng::uniform(p.seed, (unsigned)n, tick, 6u);
-      s_normal = __fmul_rn(sqrtf(__fmul_rn(-2.0f, logf(1.0f - u5))),
-                           cosf(__fmul_rn(6.2831855f, u6)));
-    } else if (tid == kWave + 1) {
-      float st[F];
-#pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
-      s_drift = Env::drift(st);
-    } else if (tid < kWave + 2 + R) {
-      const unsigned k = (unsigned)(tid - kWave - 2);
-      s_ur[k] = pdrl_rng::uniform(p.seed, (unsigned)n, tick, k + 1u);
-    }
-    // The part of the transform that needs the heads only (thread 0, which
-    // holds them) goes before the barrier, under wave 1's chains. Mode 0,
-    // PPO-C: Normal(tanh(mu), softplus(std) + 1e-4), loc = mean and ls =
-    // log(sd); mode 1, SAC-C: tanh-squashed Normal(mu, exp(clamp(log_std))),
-    // loc = mu and ls the clamped log_std.
-    float loc = 0.0f, sd = 0.0f, ls = 0.0f;
-    if (tid == 0) {
-      p.logits[row * 2] = lg[0];
-      p.logits[row * 2 + 1] = lg[1];
-      if constexpr (Mode == 0) {
-        loc = tanhf(lg[0]);
-        sd = (lg[1] > 20.0f ? lg[1] : log1pf(expf(lg[1]))) + 1e-4f;
-        ls = logf(sd);
-      } else {
-        loc = lg[0];
-        ls = fminf(fmaxf(lg[1], -20.0f), 2.0f);
-        sd = expf(ls);
-      }
-    }
-    __syncthreads();
-
-    // sample, log-prob, env step, termination, auto-reset (thread 0)
-    if (tid == 0) {
-      const float nrm = s_normal;
-      float act, lp;
-      if constexpr (Mode == 0) {
-        // the action is stored unclipped, as the workers do
-        act = __fadd_rn(loc, __fmul_rn(sd, nrm));
-        lp = -0.5f * nrm * nrm - ls - kHalfLog2Pi;
-      } else {
-        const float mu = loc;
-        float z, quad;
-        if (n < p.ou_envs || tick <= p.warmup_steps) {
-          // OU exploration: correlated noise replaces the policy sample; the
-          // log-prob is the policy's density at that action
-          ou = __fadd_rn(__fsub_rn(ou, __fmul_rn(p.ou_theta, ou)),
-                         __fmul_rn(p.ou_sigma, nrm));
-          z = ou;
-          const float q = (z - mu) / sd;
-          quad = -0.5f * (q * q);
-        } else {
-          z = __fadd_rn(mu, __fmul_rn(sd, nrm));
-          quad = -0.5f * nrm * nrm;
-        }
-        act = tanhf(z);
-        // 1 - a*a + 1e-7 without fma contraction: with the same action it
-        // equals the oracle's value to the last bit, so the logf that
-        // amplifies it (by up to 2 / (1 - a*a)) sees no extra difference
-        const float om =
-            __fadd_rn(__fsub_rn(1.0f, __fmul_rn(act, act)), 1e-7f);
-        lp = quad - ls - kHalfLog2Pi - logf(om);
-      }
-      p.act[row] = act;
-      p.log_prob[row] = lp;
-
-      float st[F];
-#pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
-      float reward;
-      bool terminated;
-      Env::step(st, act, s_drift, reward, terminated);
-      steps += 1;
-      run += reward;
-      p.rew[row] = reward;
-      const bool done = terminated || steps >= p.max_episode_steps;
-      const bool reset = done || steps >= p.time_horizon;
-      p.ep_ret[row] = reset ? run : kNoEpisode;
-      if (reset) {
-        Env::reset(st, s_ur);
-        steps = 0;
-        run = 0.0f;
-        ou = 0.0f;
-      }
-#pragma unroll
-      for (int k = 0; k < F; ++k) s_obs[k] = st[k];
-      s_fir = reset ? 1.0f : 0.0f;
-      s_reset = reset ? 1 : 0;
-    }
-    __syncthreads();
-    // thread j is the only reader of s_h[j] / s_c[j] before the next barrier
-    if (s_reset != 0 && tid < H) {
-      s_h[tid] = 0.0f;
-      s_c[tid] = 0.0f;
-    }
-  }
-
-  // persist the per-env state for the next launch
-  if (tid < H) {
-    p.h[(long)n * H + tid] = s_h[tid];
-    p.c[(long)n * H + tid] = s_c[tid];
-  }
-  if (tid < F) p.env_state[(long)n * F + tid] = s_obs[tid];
-  if (tid == 0) {
-    p.is_fir[n] = s_fir;
-    p.ep_steps[n] = steps;
-    p.ep_run[n] = run;
-    p.tick[n] = tick;
-    if constexpr (Mode == 1) p.ou_state[n] = ou;
-  }
-}
-
-// ---- greedy evaluation: whole episodes in one launch ----------------------
-// rollout_eval_discrete / rollout_eval_gaussian run E episodes per env back
-// to back under the deterministic action (arg-max logit; tanh(mu)) and write
-// one return and one length per (env, episode). Geometry, weight residency
-// and the wave 0 / wave 1 overlap are those of the training kernels; what is
-// gone is everything a batch needs: no (N, S, ·) record, no softmax, no
-// log-prob, no sampling draw, no OU state — and nothing persistent is read or
-// written, so a launch cannot disturb the training envs. Episode e of env n
-// starts from Env::reset of hash tick e (lanes 1..draws) with h = c = 0, a
-// pure function of (seed, n, e); ``start_state`` may replace the start of
-// episode 0. An episode ends on ``terminated`` or at max_episode_steps.
-//
-// The step loop is bounded by E * max_episode_steps (every episode takes at
-// most max_episode_steps steps, so that many iterations finish all of them);
-// the workgroup-uniform control word in LDS only leaves it early.
+// Arguments of rollout_eval (see there).
 struct EvalArgs : PolicyWeights {
   const float* start_state;  // (N, F) start of episode 0, or nullptr
   float* ep_ret;             // (N, E)
@@ -703,180 +364,540 @@ struct EvalArgs : PolicyWeights {
 // control word written by thread 0 at the end of a step
 constexpr int kEvalGoOn = 0, kEvalNextEpisode = 1, kEvalAllDone = 2;
 
-template <int H, typename Env>
-__global__ __launch_bounds__(4 * H) void rollout_eval_discrete(EvalArgs p) {
-  constexpr int G = 4 * H;
-  constexpr int F = Env::kObsDim;
-  constexpr int A = Env::kActions;
-  static_assert(F <= 4, "reset draws use hash lanes 1..4");
-  const int tid = threadIdx.x;
-  const int n = blockIdx.x;
-  if (n >= p.N) return;  // uniform per workgroup
+// ---- LDS and step parts shared by both kernels -----------------------------
+// The LDS block of a kernel: the recurrent part (b128 broadcast reads, hence
+// the alignment), the K leading head columns ([a][k]), the env state and the
+// reset uniforms of the step. Separate arrays on purpose: as members of one
+// struct they cost the Gaussian rollout about 1 % (the compiler lays out and
+// addresses separate arrays better; profiles/device_rollout.md).
+#define PDRL_ROLLOUT_LDS(H, F, K, R)                              \
+  __shared__ __attribute__((aligned(16))) float s_xb[H];         \
+  __shared__ __attribute__((aligned(16))) float s_h[H];          \
+  __shared__ __attribute__((aligned(16))) float s_c[H];          \
+  __shared__ __attribute__((aligned(16))) float s_gates[4 * H];  \
+  __shared__ float s_hw[K * H];                                  \
+  __shared__ float s_obs[F];                                     \
+  __shared__ float s_ur[R]
 
-  __shared__ __attribute__((aligned(16))) float s_xb[H];
-  __shared__ __attribute__((aligned(16))) float s_h[H];
-  __shared__ __attribute__((aligned(16))) float s_c[H];
-  __shared__ __attribute__((aligned(16))) float s_gates[G];
-  __shared__ float s_hw[A * H];  // logits head columns, [a][k]
-  __shared__ float s_obs[F];
-  __shared__ float s_cand[A * F];  // next state for every action
-  __shared__ float s_crew[A];
-  __shared__ int s_cterm[A];
-  __shared__ float s_ur[F];  // start state uniforms of the next episode
-  __shared__ int s_ctl;
-
-  RecurrentCore<H, F> core;
-  core.load_weights(p, tid);
-  float hb[A];
+// Head biases into registers (every thread), head columns into LDS.
+template <int H, int K>
+__device__ __forceinline__ void stage_heads(const PolicyWeights& p, int D,
+                                            int tid, float* s_hw,
+                                            float (&hb)[K]) {
 #pragma unroll
-  for (int a = 0; a < A; ++a) hb[a] = p.heads_b[a];
-  for (int idx = tid; idx < A * H; idx += G) {
+  for (int a = 0; a < K; ++a) hb[a] = p.heads_b[a];
+  for (int idx = tid; idx < K * H; idx += 4 * H) {
     const int a = idx / H, k = idx % H;
-    s_hw[idx] = p.heads_w[k * p.D + a];
+    s_hw[idx] = p.heads_w[k * D + a];
   }
+}
+
+// Wave 0: the K head outputs. The H-long dot products are split over the
+// lanes and butterfly-reduced (a serial loop in one lane is ~H dependent LDS
+// round trips — it dominated the step). Static indices: lg stays in VGPRs.
+template <int H, int K>
+__device__ __forceinline__ void reduce_heads(const float* s_h,
+                                             const float* s_hw,
+                                             const float (&hb)[K], int lane,
+                                             float (&lg)[K]) {
+#pragma unroll
+  for (int a = 0; a < K; ++a) {
+    float part = 0.0f;
+    for (int k = lane; k < H; k += kWave)
+      part = fmaf(s_h[k], s_hw[a * H + k], part);
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1)
+      part += __shfl_xor(part, off, kWave);
+    lg[a] = part + hb[a];
+  }
+}
+
+// Fresh recurrent state. Thread j is the only reader of s_h[j] / s_c[j]
+// before the next barrier.
+template <int H>
+__device__ __forceinline__ void zero_recurrent(int tid, float* s_h,
+                                               float* s_c) {
   if (tid < H) {
     s_h[tid] = 0.0f;
     s_c[tid] = 0.0f;
   }
-  if (tid == 0) {
-    float st[F];
-    if (p.start_state != nullptr) {
-#pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = p.start_state[(long)n * F + k];
-    } else {
-      float u[F];
-#pragma unroll
-      for (int k = 0; k < F; ++k)
-        u[k] = pdrl_rng::uniform(p.seed, (unsigned)n, 0u, (unsigned)k + 1u);
-      Env::reset(st, u);
-    }
-#pragma unroll
-    for (int k = 0; k < F; ++k) s_obs[k] = st[k];
-  }
-  __syncthreads();
+}
 
-  // every thread tracks the episode index (hash counter of the next start
-  // state); the step count and the running return live in thread 0
-  int episode = 0, steps = 0;
-  float run = 0.0f;
-  const int max_iters = p.E * p.max_episode_steps;  // <= 2^22 (binding)
-  for (int it = 0; it < max_iters; ++it) {
-    core.advance(p, tid, s_obs, s_xb, s_h, s_c, s_gates);
+// Side lane k of [0, R): uniform k of a reset keyed by counter ``ctr``.
+template <int R>
+__device__ __forceinline__ void draw_reset_uniform(int k, float* s_ur,
+                                                   unsigned seed, int n,
+                                                   unsigned ctr) {
+  if (k < R)
+    s_ur[k] = pdrl_rng::uniform(seed, (unsigned)n, ctr, (unsigned)k + 1u);
+}
 
-    float lg[A];
-    if (tid < kWave) {
-      // logits: wave 0 splits the H-long dot products over its lanes and
-      // butterfly-reduces them, exactly as rollout_discrete does
-#pragma unroll
-      for (int a = 0; a < A; ++a) {
-        float part = 0.0f;
-        for (int k = tid; k < H; k += kWave)
-          part = fmaf(s_h[k], s_hw[a * H + k], part);
-#pragma unroll
-        for (int off = kWave / 2; off > 0; off >>= 1)
-          part += __shfl_xor(part, off, kWave);
-        lg[a] = part + hb[a];
-      }
-    } else if (tid < kWave + A) {
-      // meanwhile wave 1 steps the dynamics for every action (lane = action)
-      const int a = tid - kWave;
+// ---- policy schemes ---------------------------------------------------------
+// A scheme is what differs between the kernels' instances. Every scheme has
+//   Env, kHeads   the env traits; the number of leading head columns read
+//   Lds           its private LDS, written by side(), read by post()
+//   Choice        what thread 0 carries over the fourth barrier
+//   side(lane, s_obs, lds, s_ur, seed, n, ctr)
+//                 wave 1 (lane = tid - kWave) while wave 0 reduces the heads:
+//                 dynamics that need no action yet, random draws, and the
+//                 uniforms of a reset caused by this step (hash counter ctr)
+// A sampling scheme (rollout_train) also has Args, Regs (thread-0 registers
+// carried over the steps and, through load / store, over the launches) and
+//   pre(p, row, n, tick, lg, ch)      thread 0, before the barrier: what
+//                 needs the heads only; records ``logits``
+//   post(p, row, n, tick, ch, regs, lds, s_obs, st, reward, terminated)
+//                 thread 0, after it: records ``act`` and ``log_prob`` (or
+//                 pre did), yields the step's outcome
+// and a greedy scheme (rollout_eval), which records nothing,
+//   pre(lg, ch) and post(ch, lds, s_obs, st, reward, terminated).
+// The precise libm forms throughout: parity of the sample against the oracle
+// is what the tests measure.
+
+struct NoRegs {
+  template <typename Args>
+  __device__ __forceinline__ void load(const Args&, int) {}
+  template <typename Args>
+  __device__ __forceinline__ void store(const Args&, int) const {}
+  __device__ __forceinline__ void reset() {}
+};
+
+// Categorical policy over a discrete env. Wave 1 steps the dynamics for
+// EVERY action (lane = action) and draws the reset uniforms, so thread 0's
+// scalar chain (softmax / sample / log-prob, or the arg-max) and the env's
+// (sin / cos / divides) run side by side; post only picks a candidate.
+template <typename EnvT>
+struct CategoricalBase {
+  using Env = EnvT;
+  static constexpr int F = Env::kObsDim;
+  static constexpr int A = Env::kActions;
+  static constexpr int kHeads = A;
+
+  struct Lds {
+    alignas(16) float cand[A * F];  // next state for every action
+    float crew[A];
+    int cterm[A];
+  };
+  struct Choice {
+    int chosen = 0;
+  };
+
+  __device__ __forceinline__ static void side(int lane, const float* s_obs,
+                                              Lds& s, float* s_ur,
+                                              unsigned seed, int n,
+                                              unsigned ctr) {
+    if (lane < A) {
       float st[F];
 #pragma unroll
       for (int k = 0; k < F; ++k) st[k] = s_obs[k];
       float reward;
       bool terminated;
-      Env::step(st, a, reward, terminated);
+      Env::step(st, lane, reward, terminated);
 #pragma unroll
-      for (int k = 0; k < F; ++k) s_cand[a * F + k] = st[k];
-      s_crew[a] = reward;
-      s_cterm[a] = terminated ? 1 : 0;
-    } else if (tid < kWave + A + F) {
-      // ... and draws the start state of the episode that would follow
-      const unsigned k = (unsigned)(tid - kWave - A);
-      s_ur[k] = pdrl_rng::uniform(p.seed, (unsigned)n,
-                                  (unsigned)episode + 1u, k + 1u);
+      for (int k = 0; k < F; ++k) s.cand[lane * F + k] = st[k];
+      s.crew[lane] = reward;
+      s.cterm[lane] = terminated ? 1 : 0;
+    } else {
+      draw_reset_uniform<Env::kResetDraws>(lane - A, s_ur, seed, n, ctr);
     }
+  }
 
-    // greedy action (thread 0 holds the reduced logits): strict > scan from
-    // action 0, so ties go to the lowest index
-    int chosen = 0;
-    if (tid == 0) {
-      float best = lg[0];
+  // greedy form of post(); the sampling scheme forwards to it
+  __device__ __forceinline__ static void post(const Choice& ch, const Lds& s,
+                                              const float*, float* st,
+                                              float& reward,
+                                              bool& terminated) {
 #pragma unroll
-      for (int a = 1; a < A; ++a) {
-        if (lg[a] > best) {
-          best = lg[a];
-          chosen = a;
-        }
+    for (int k = 0; k < F; ++k) st[k] = s.cand[ch.chosen * F + k];
+    reward = s.crew[ch.chosen];
+    terminated = s.cterm[ch.chosen] != 0;
+  }
+};
+
+// Softmax, inverse-CDF sample against hash lane 0, log-prob.
+template <typename EnvT>
+struct CategoricalSample : CategoricalBase<EnvT> {
+  using Base = CategoricalBase<EnvT>;
+  using Args = RolloutArgs;
+  using Regs = NoRegs;
+  using typename Base::Choice;
+  using typename Base::Lds;
+  static constexpr int A = Base::A;
+
+  __device__ __forceinline__ static void pre(const Args& p, long row, int n,
+                                             unsigned tick,
+                                             const float (&lg)[A],
+                                             Choice& ch) {
+    float mx = lg[0];
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+      p.logits[row * A + a] = lg[a];
+      mx = fmaxf(mx, lg[a]);
+    }
+    float prob[A];
+    float Z = 0.0f;
+#pragma unroll
+    for (int a = 0; a < A; ++a) {
+      prob[a] = expf(lg[a] - mx);
+      Z += prob[a];
+    }
+    // inverse CDF against one uniform (rule of cpu_actor.cpp)
+    const float u = pdrl_rng::uniform(p.seed, (unsigned)n, tick, 0u);
+    float cdf = 0.0f;
+    bool found = false;
+    int chosen = A - 1;
+    float lg_chosen = lg[A - 1];
+#pragma unroll
+    for (int a = 0; a < A; ++a) {  // static indices: lg/prob stay in VGPRs
+      cdf += prob[a] / Z;
+      if (!found && u < cdf) {
+        chosen = a;
+        lg_chosen = lg[a];
+        found = true;
       }
     }
-    __syncthreads();
+    ch.chosen = chosen;
+    p.act[row] = (float)chosen;
+    p.log_prob[row] = lg_chosen - mx - logf(Z);
+  }
 
-    // the chosen action's outcome; episode end and fresh start (thread 0)
-    if (tid == 0) {
-      float st[F];
+  __device__ __forceinline__ static void post(const Args&, long, int, unsigned,
+                                              const Choice& ch, Regs&,
+                                              const Lds& s, const float*,
+                                              float* st, float& reward,
+                                              bool& terminated) {
+    Base::post(ch, s, nullptr, st, reward, terminated);
+  }
+};
+
+// Arg-max logit: strict > scan from action 0, so ties go to the lowest index.
+template <typename EnvT>
+struct CategoricalGreedy : CategoricalBase<EnvT> {
+  using Base = CategoricalBase<EnvT>;
+  using typename Base::Choice;
+  using typename Base::Lds;
+  static constexpr int A = Base::A;
+
+  __device__ __forceinline__ static void pre(const float (&lg)[A],
+                                             Choice& ch) {
+    float best = lg[0];
 #pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = s_cand[chosen * F + k];
-      steps += 1;
-      run += s_crew[chosen];
-      const bool done = s_cterm[chosen] != 0 || steps >= p.max_episode_steps;
-      int ctl = kEvalGoOn;
-      if (done) {
-        p.ep_ret[(long)n * p.E + episode] = run;
-        p.ep_len[(long)n * p.E + episode] = steps;
-        Env::reset(st, s_ur);
-        steps = 0;
-        run = 0.0f;
-        ctl = (episode + 1 >= p.E) ? kEvalAllDone : kEvalNextEpisode;
-      }
-#pragma unroll
-      for (int k = 0; k < F; ++k) s_obs[k] = st[k];
-      s_ctl = ctl;
-    }
-    __syncthreads();
-    const int ctl = s_ctl;  // the same value in every thread of the workgroup
-    if (ctl == kEvalAllDone) break;
-    if (ctl == kEvalNextEpisode) {
-      episode += 1;
-      // thread j is the only reader of s_h[j] / s_c[j] before the next barrier
-      if (tid < H) {
-        s_h[tid] = 0.0f;
-        s_c[tid] = 0.0f;
+    for (int a = 1; a < A; ++a) {
+      if (lg[a] > best) {
+        best = lg[a];
+        ch.chosen = a;
       }
     }
   }
-}
+};
 
-template <int H, typename Env>
-__global__ __launch_bounds__(4 * H) void rollout_eval_gaussian(EvalArgs p) {
-  static_assert(Env::kActDim == 1, "one action dimension (head column 0)");
-  static_assert(Env::kResetDraws >= 1 && Env::kResetDraws <= 4,
-                "reset draws use hash lanes 1..4");
+// Gaussian policy over a continuous env, action of width 1: head column 0 is
+// mu. One side lane evaluates the env's action-independent drift, kResetDraws
+// lanes draw the reset uniforms; thread 0 steps the one chosen action.
+template <typename EnvT>
+struct GaussianBase {
+  using Env = EnvT;
+  static constexpr int F = Env::kObsDim;
+  // One tick has eight hash lanes: 1..4 reset, 5 / 6 the normal. A second
+  // action dimension needs a wider counter (rollout_rng.h).
+  static_assert(Env::kActDim == 1,
+                "eight hash lanes per tick allow exactly one action dimension");
+
+  __device__ __forceinline__ static void env_side(int lane, const float* s_obs,
+                                                  float& s_drift, float* s_ur,
+                                                  unsigned seed, int n,
+                                                  unsigned ctr) {
+    if (lane == 0) {
+      float st[F];
+#pragma unroll
+      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+      s_drift = Env::drift(st);
+    } else {
+      draw_reset_uniform<Env::kResetDraws>(lane - 1, s_ur, seed, n, ctr);
+    }
+  }
+
+  __device__ __forceinline__ static void env_step(const float* s_obs,
+                                                  float act, float drift,
+                                                  float* st, float& reward,
+                                                  bool& terminated) {
+#pragma unroll
+    for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+    Env::step(st, act, drift, reward, terminated);
+  }
+};
+
+// Sampling schemes of cpu_actor.cpp::act_batch_gaussian. Heads: column 0 =
+// mu, column 1 = std (Mode 0, PPO-C) or log_std (Mode 1, SAC-C); the
+// ``logits`` field is [mu_raw | second_raw], ``act`` has width 1. Side lane 0
+// turns hash lanes 5 / 6 into the step's standard normal (log / sqrt / cos).
+template <typename EnvT, int Mode>
+struct GaussianSample : GaussianBase<EnvT> {
+  static_assert(Mode == 0 || Mode == 1, "Mode: 0 = PPO-C, 1 = SAC-C");
+  using Base = GaussianBase<EnvT>;
+  using Args = GaussianArgs;
+  static constexpr int kHeads = 2;
+  static constexpr float kHalfLog2Pi = 0.9189385f;
+
+  struct Lds {
+    float normal;
+    float drift;
+  };
+  struct Choice {
+    float loc = 0.0f, sd = 0.0f, ls = 0.0f;
+  };
+  struct Regs {  // the OU exploration state (Mode 1)
+    float ou = 0.0f;
+    __device__ __forceinline__ void load(const Args& p, int n) {
+      if constexpr (Mode == 1) ou = p.ou_state[n];
+    }
+    __device__ __forceinline__ void store(const Args& p, int n) const {
+      if constexpr (Mode == 1) p.ou_state[n] = ou;
+    }
+    __device__ __forceinline__ void reset() { ou = 0.0f; }
+  };
+
+  __device__ __forceinline__ static void side(int lane, const float* s_obs,
+                                              Lds& s, float* s_ur,
+                                              unsigned seed, int n,
+                                              unsigned ctr) {
+    if (lane == 0) {
+      // Box-Muller on hash lanes 5 (radius) and 6 (angle); 1 - u5 is exact
+      // in fp32 and never 0
+      const float u5 = pdrl_rng::uniform(seed, (unsigned)n, ctr, 5u);
+      const float u6 = pdrl_rng::uniform(seed, (unsigned)n, ctr, 6u);
+      s.normal = __fmul_rn(sqrtf(__fmul_rn(-2.0f, logf(1.0f - u5))),
+                           cosf(__fmul_rn(6.2831855f, u6)));
+    } else {
+      Base::env_side(lane - 1, s_obs, s.drift, s_ur, seed, n, ctr);
+    }
+  }
+
+  // Mode 0, PPO-C: Normal(tanh(mu), softplus(std) + 1e-4), loc = mean and
+  // ls = log(sd); mode 1, SAC-C: tanh-squashed Normal(mu, exp(clamp(log_std))),
+  // loc = mu and ls the clamped log_std. Runs under wave 1's chains.
+  __device__ __forceinline__ static void pre(const Args& p, long row, int,
+                                             unsigned, const float (&lg)[2],
+                                             Choice& ch) {
+    p.logits[row * 2] = lg[0];
+    p.logits[row * 2 + 1] = lg[1];
+    if constexpr (Mode == 0) {
+      ch.loc = tanhf(lg[0]);
+      ch.sd = (lg[1] > 20.0f ? lg[1] : log1pf(expf(lg[1]))) + 1e-4f;
+      ch.ls = logf(ch.sd);
+    } else {
+      ch.loc = lg[0];
+      ch.ls = fminf(fmaxf(lg[1], -20.0f), 2.0f);
+      ch.sd = expf(ch.ls);
+    }
+  }
+
+  // sample, log-prob, env step
+  __device__ __forceinline__ static void post(const Args& p, long row, int n,
+                                              unsigned tick, const Choice& ch,
+                                              Regs& regs, const Lds& s,
+                                              const float* s_obs, float* st,
+                                              float& reward,
+                                              bool& terminated) {
+    const float nrm = s.normal;
+    float act, lp;
+    if constexpr (Mode == 0) {
+      // the action is stored unclipped, as the workers do
+      act = __fadd_rn(ch.loc, __fmul_rn(ch.sd, nrm));
+      lp = -0.5f * nrm * nrm - ch.ls - kHalfLog2Pi;
+    } else {
+      const float mu = ch.loc;
+      float z, quad;
+      if (n < p.ou_envs || tick <= p.warmup_steps) {
+        // OU exploration: correlated noise replaces the policy sample; the
+        // log-prob is the policy's density at that action
+        regs.ou = __fadd_rn(__fsub_rn(regs.ou, __fmul_rn(p.ou_theta, regs.ou)),
+                            __fmul_rn(p.ou_sigma, nrm));
+        z = regs.ou;
+        const float q = (z - mu) / ch.sd;
+        quad = -0.5f * (q * q);
+      } else {
+        z = __fadd_rn(mu, __fmul_rn(ch.sd, nrm));
+        quad = -0.5f * nrm * nrm;
+      }
+      act = tanhf(z);
+      // 1 - a*a + 1e-7 without fma contraction: with the same action it
+      // equals the oracle's value to the last bit, so the logf that
+      // amplifies it (by up to 2 / (1 - a*a)) sees no extra difference
+      const float om =
+          __fadd_rn(__fsub_rn(1.0f, __fmul_rn(act, act)), 1e-7f);
+      lp = quad - ch.ls - kHalfLog2Pi - logf(om);
+    }
+    p.act[row] = act;
+    p.log_prob[row] = lp;
+    Base::env_step(s_obs, act, s.drift, st, reward, terminated);
+  }
+};
+
+// tanh(mu): the mean of PPO-C's Normal(tanh(mu), ·) and of SAC-C's squashed
+// Gaussian at zero noise, so only head column 0 is read.
+template <typename EnvT>
+struct GaussianGreedy : GaussianBase<EnvT> {
+  using Base = GaussianBase<EnvT>;
+  static constexpr int kHeads = 1;
+
+  struct Lds {
+    float drift;
+  };
+  struct Choice {
+    float act = 0.0f;
+  };
+
+  __device__ __forceinline__ static void side(int lane, const float* s_obs,
+                                              Lds& s, float* s_ur,
+                                              unsigned seed, int n,
+                                              unsigned ctr) {
+    Base::env_side(lane, s_obs, s.drift, s_ur, seed, n, ctr);
+  }
+
+  __device__ __forceinline__ static void pre(const float (&lg)[1],
+                                             Choice& ch) {
+    ch.act = tanhf(lg[0]);
+  }
+
+  __device__ __forceinline__ static void post(const Choice& ch, const Lds& s,
+                                              const float* s_obs, float* st,
+                                              float& reward,
+                                              bool& terminated) {
+    Base::env_step(s_obs, ch.act, s.drift, st, reward, terminated);
+  }
+};
+
+// ---- training rollout: S steps of every env, (N, S, ·) batch ---------------
+template <int H, typename Policy>
+__global__ __launch_bounds__(4 * H) void rollout_train(
+    typename Policy::Args p) {
+  using Env = typename Policy::Env;
   constexpr int F = Env::kObsDim;
+  constexpr int K = Policy::kHeads;
   constexpr int R = Env::kResetDraws;
-  constexpr int G = 4 * H;
+  static_assert(R >= 1 && R <= 4, "reset draws use hash lanes 1..4");
   const int tid = threadIdx.x;
   const int n = blockIdx.x;
   if (n >= p.N) return;  // uniform per workgroup
 
-  __shared__ __attribute__((aligned(16))) float s_xb[H];
-  __shared__ __attribute__((aligned(16))) float s_h[H];
-  __shared__ __attribute__((aligned(16))) float s_c[H];
-  __shared__ __attribute__((aligned(16))) float s_gates[G];
-  __shared__ float s_hw[H];  // mu head column
-  __shared__ float s_obs[F];
-  __shared__ float s_ur[R];  // start state uniforms of the next episode
-  __shared__ float s_drift;
+  PDRL_ROLLOUT_LDS(H, F, K, R);
+  __shared__ typename Policy::Lds sp;
+  __shared__ float s_fir;
+  __shared__ int s_reset;
+
+  RecurrentCore<H, F> core;
+  core.load(p, tid, n, s_h, s_c);
+  float hb[K];
+  stage_heads<H, K>(p, p.D, tid, s_hw, hb);
+  if (tid < F) s_obs[tid] = p.env_state[(long)n * F + tid];
+
+  // episode bookkeeping and the scheme's registers live in thread 0 across
+  // the S steps
+  int steps = 0;
+  float run = 0.0f;
+  typename Policy::Regs regs;
+  unsigned tick = p.tick[n];  // every thread tracks it (hash counter)
+  if (tid == 0) {
+    s_fir = p.is_fir[n];
+    steps = p.ep_steps[n];
+    run = p.ep_run[n];
+    regs.load(p, n);
+  }
+  __syncthreads();
+
+  for (int t = 0; t < p.S; ++t) {
+    const long row = (long)n * p.S + t;
+    tick += 1u;
+    // record the pre-step obs / hx / cx / is_fir; body, gates, cell update
+    core.step(p, tid, row, s_obs, &s_fir, s_xb, s_h, s_c, s_gates);
+
+    float lg[K];
+    if (tid < kWave)
+      reduce_heads<H, K>(s_h, s_hw, hb, tid, lg);
+    else
+      Policy::side(tid - kWave, s_obs, sp, s_ur, p.seed, n, tick);
+    // thread 0 already holds the reduced heads: no barrier needed
+    typename Policy::Choice ch;
+    if (tid == 0) Policy::pre(p, row, n, tick, lg, ch);
+    __syncthreads();
+
+    // the step's outcome; termination, auto-reset (thread 0)
+    if (tid == 0) {
+      float st[F];
+      float reward;
+      bool terminated;
+      Policy::post(p, row, n, tick, ch, regs, sp, s_obs, st, reward,
+                   terminated);
+      steps += 1;
+      run += reward;
+      p.rew[row] = reward;
+      const bool done = terminated || steps >= p.max_episode_steps;
+      const bool reset = done || steps >= p.time_horizon;
+      p.ep_ret[row] = reset ? run : kNoEpisode;
+      if (reset) {
+        Env::reset(st, s_ur);
+        steps = 0;
+        run = 0.0f;
+        regs.reset();
+      }
+#pragma unroll
+      for (int k = 0; k < F; ++k) s_obs[k] = st[k];
+      s_fir = reset ? 1.0f : 0.0f;
+      s_reset = reset ? 1 : 0;
+    }
+    __syncthreads();
+    if (s_reset != 0) zero_recurrent<H>(tid, s_h, s_c);
+  }
+
+  // persist the per-env state for the next launch
+  if (tid < H) {
+    p.h[(long)n * H + tid] = s_h[tid];
+    p.c[(long)n * H + tid] = s_c[tid];
+  }
+  if (tid < F) p.env_state[(long)n * F + tid] = s_obs[tid];
+  if (tid == 0) {
+    p.is_fir[n] = s_fir;
+    p.ep_steps[n] = steps;
+    p.ep_run[n] = run;
+    p.tick[n] = tick;
+    regs.store(p, n);
+  }
+}
+
+// ---- greedy evaluation: whole episodes in one launch ------------------------
+// E episodes per env back to back under the scheme's deterministic action;
+// one return and one length per (env, episode). Geometry, weight residency
+// and the wave 0 / wave 1 overlap are those of rollout_train; what is gone is
+// everything a batch needs: no (N, S, ·) record, no softmax, no log-prob, no
+// sampling draw, no OU state — and nothing persistent is read or written, so
+// a launch cannot disturb the training envs. Episode e of env n starts from
+// Env::reset of hash tick e (lanes 1..draws) with h = c = 0, a pure function
+// of (seed, n, e); ``start_state`` may replace the start of episode 0. An
+// episode ends on ``terminated`` or at max_episode_steps.
+//
+// The step loop is bounded by E * max_episode_steps (every episode takes at
+// most max_episode_steps steps, so that many iterations finish all of them);
+// the workgroup-uniform control word in LDS only leaves it early.
+template <int H, typename Policy>
+__global__ __launch_bounds__(4 * H) void rollout_eval(EvalArgs p) {
+  using Env = typename Policy::Env;
+  constexpr int F = Env::kObsDim;
+  constexpr int K = Policy::kHeads;
+  constexpr int R = Env::kResetDraws;
+  static_assert(R >= 1 && R <= 4, "reset draws use hash lanes 1..4");
+  const int tid = threadIdx.x;
+  const int n = blockIdx.x;
+  if (n >= p.N) return;  // uniform per workgroup
+
+  PDRL_ROLLOUT_LDS(H, F, K, R);  // s_ur: start state of the next episode
+  __shared__ typename Policy::Lds sp;
   __shared__ int s_ctl;
 
   RecurrentCore<H, F> core;
   core.load_weights(p, tid);
-  const float hb = p.heads_b[0];
-  if (tid < H) {
-    s_hw[tid] = p.heads_w[tid * p.D];
-    s_h[tid] = 0.0f;
-    s_c[tid] = 0.0f;
-  }
+  float hb[K];
+  stage_heads<H, K>(p, p.D, tid, s_hw, hb);
+  zero_recurrent<H>(tid, s_h, s_c);
   if (tid == 0) {
     float st[F];
     if (p.start_state != nullptr) {
@@ -894,48 +915,30 @@ __global__ __launch_bounds__(4 * H) void rollout_eval_gaussian(EvalArgs p) {
   }
   __syncthreads();
 
+  // every thread tracks the episode index (hash counter of the next start
+  // state); the step count and the running return live in thread 0
   int episode = 0, steps = 0;
   float run = 0.0f;
   const int max_iters = p.E * p.max_episode_steps;  // <= 2^22 (binding)
   for (int it = 0; it < max_iters; ++it) {
     core.advance(p, tid, s_obs, s_xb, s_h, s_c, s_gates);
 
-    float mu = 0.0f;
-    if (tid < kWave) {
-      // the mu head column only: wave 0 butterfly-reduces the dot product
-      float part = 0.0f;
-      for (int k = tid; k < H; k += kWave)
-        part = fmaf(s_h[k], s_hw[k], part);
-#pragma unroll
-      for (int off = kWave / 2; off > 0; off >>= 1)
-        part += __shfl_xor(part, off, kWave);
-      mu = part + hb;
-    } else if (tid == kWave) {
-      // meanwhile wave 1 evaluates the action-independent drift
-      float st[F];
-#pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
-      s_drift = Env::drift(st);
-    } else if (tid < kWave + 1 + R) {
-      // ... and draws the start state of the episode that would follow
-      const unsigned k = (unsigned)(tid - kWave - 1);
-      s_ur[k] = pdrl_rng::uniform(p.seed, (unsigned)n,
-                                  (unsigned)episode + 1u, k + 1u);
-    }
-    // deterministic action of both head schemes: the mean of PPO-C's
-    // Normal(tanh(mu), ·) and of SAC-C's squashed Gaussian at zero noise
-    float act = 0.0f;
-    if (tid == 0) act = tanhf(mu);
+    float lg[K];
+    if (tid < kWave)
+      reduce_heads<H, K>(s_h, s_hw, hb, tid, lg);
+    else
+      Policy::side(tid - kWave, s_obs, sp, s_ur, p.seed, n,
+                   (unsigned)episode + 1u);
+    typename Policy::Choice ch;
+    if (tid == 0) Policy::pre(lg, ch);
     __syncthreads();
 
-    // env step, episode end and fresh start (thread 0)
+    // the step's outcome; episode end and fresh start (thread 0)
     if (tid == 0) {
       float st[F];
-#pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
       float reward;
       bool terminated;
-      Env::step(st, act, s_drift, reward, terminated);
+      Policy::post(ch, sp, s_obs, st, reward, terminated);
       steps += 1;
       run += reward;
       const bool done = terminated || steps >= p.max_episode_steps;
@@ -957,102 +960,41 @@ __global__ __launch_bounds__(4 * H) void rollout_eval_gaussian(EvalArgs p) {
     if (ctl == kEvalAllDone) break;
     if (ctl == kEvalNextEpisode) {
       episode += 1;
-      // thread j is the only reader of s_h[j] / s_c[j] before the next barrier
-      if (tid < H) {
-        s_h[tid] = 0.0f;
-        s_c[tid] = 0.0f;
-      }
+      zero_recurrent<H>(tid, s_h, s_c);
     }
   }
 }
 
-template <typename Env>
-void launch_eval_discrete(const EvalArgs& a, int H) {
-  const dim3 grid(a.N);
+// ---- host side --------------------------------------------------------------
+// f(std::integral_constant<int, H>) launches one kernel for the hidden size.
+template <typename Fn>
+void dispatch_hidden(int H, Fn&& f) {
   switch (H) {
-    case 32:
-      hipLaunchKernelGGL((rollout_eval_discrete<32, Env>), grid, dim3(128), 0,
-                         current_stream(), a);
-      break;
-    case 64:
-      hipLaunchKernelGGL((rollout_eval_discrete<64, Env>), grid, dim3(256), 0,
-                         current_stream(), a);
-      break;
-    case 128:
-      hipLaunchKernelGGL((rollout_eval_discrete<128, Env>), grid, dim3(512), 0,
-                         current_stream(), a);
-      break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 64: f(std::integral_constant<int, 64>{}); break;
+    case 128: f(std::integral_constant<int, 128>{}); break;
     default:
       TORCH_CHECK(false, "hidden size ", H, " unsupported (32/64/128)");
   }
   HIP_CHECK_LAST();
 }
 
-template <typename Env>
-void launch_eval_gaussian(const EvalArgs& a, int H) {
-  const dim3 grid(a.N);
-  switch (H) {
-    case 32:
-      hipLaunchKernelGGL((rollout_eval_gaussian<32, Env>), grid, dim3(128), 0,
-                         current_stream(), a);
-      break;
-    case 64:
-      hipLaunchKernelGGL((rollout_eval_gaussian<64, Env>), grid, dim3(256), 0,
-                         current_stream(), a);
-      break;
-    case 128:
-      hipLaunchKernelGGL((rollout_eval_gaussian<128, Env>), grid, dim3(512), 0,
-                         current_stream(), a);
-      break;
-    default:
-      TORCH_CHECK(false, "hidden size ", H, " unsupported (32/64/128)");
-  }
-  HIP_CHECK_LAST();
+template <typename Policy>
+void launch_train(const typename Policy::Args& a, int H) {
+  dispatch_hidden(H, [&](auto h) {
+    constexpr int kH = decltype(h)::value;
+    hipLaunchKernelGGL((rollout_train<kH, Policy>), dim3(a.N), dim3(4 * kH),
+                       0, current_stream(), a);
+  });
 }
 
-template <int H, typename Env>
-void launch_gaussian_mode(const GaussianArgs& a, int mode) {
-  const dim3 grid(a.N), block(4 * H);
-  if (mode == 0)
-    hipLaunchKernelGGL((rollout_gaussian<H, Env, 0>), grid, block, 0,
+template <typename Policy>
+void launch_eval(const EvalArgs& a, int H) {
+  dispatch_hidden(H, [&](auto h) {
+    constexpr int kH = decltype(h)::value;
+    hipLaunchKernelGGL((rollout_eval<kH, Policy>), dim3(a.N), dim3(4 * kH), 0,
                        current_stream(), a);
-  else
-    hipLaunchKernelGGL((rollout_gaussian<H, Env, 1>), grid, block, 0,
-                       current_stream(), a);
-}
-
-template <typename Env>
-void launch_gaussian(const GaussianArgs& a, int H, int mode) {
-  switch (H) {
-    case 32: launch_gaussian_mode<32, Env>(a, mode); break;
-    case 64: launch_gaussian_mode<64, Env>(a, mode); break;
-    case 128: launch_gaussian_mode<128, Env>(a, mode); break;
-    default:
-      TORCH_CHECK(false, "hidden size ", H, " unsupported (32/64/128)");
-  }
-  HIP_CHECK_LAST();
-}
-
-template <typename Env>
-void launch_env(const RolloutArgs& a, int H) {
-  const dim3 grid(a.N);
-  switch (H) {
-    case 32:
-      hipLaunchKernelGGL((rollout_discrete<32, Env>), grid, dim3(128), 0,
-                         current_stream(), a);
-      break;
-    case 64:
-      hipLaunchKernelGGL((rollout_discrete<64, Env>), grid, dim3(256), 0,
-                         current_stream(), a);
-      break;
-    case 128:
-      hipLaunchKernelGGL((rollout_discrete<128, Env>), grid, dim3(512), 0,
-                         current_stream(), a);
-      break;
-    default:
-      TORCH_CHECK(false, "hidden size ", H, " unsupported (32/64/128)");
-  }
-  HIP_CHECK_LAST();
+  });
 }
 
 void check_i32(const at::Tensor& t, long n, const char* name) {
@@ -1221,7 +1163,7 @@ EvalArgs pack_eval_args(
 
 }  // namespace
 
-// env_id: 0 = CartPole-v1 (ids are assigned in pdrl_amd/ops/rollout.py).
+// Categorical policy. env_id: see with_discrete_env.
 void rollout_discrete_hip(
     const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
     const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
@@ -1232,30 +1174,20 @@ void rollout_discrete_hip(
     at::Tensor& is_fir_out, at::Tensor& hx, at::Tensor& cx,
     at::Tensor& ep_ret, long env_id, long seed, long time_horizon,
     long max_episode_steps) {
-  long F_env = 0, A = 0;
-  const char* env_msg = "";
-  switch (env_id) {
-    case 0:
-      F_env = CartPoleDyn::kObsDim;
-      A = CartPoleDyn::kActions;
-      env_msg = "CartPole needs obs_dim 4";
-      break;
-    default:
-      TORCH_CHECK(false, "rollout: unknown device env id ", env_id);
-  }
-  const RolloutArgs a = pack_rollout_args(
-      body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, env_state, h, c,
-      is_fir, ep_steps, ep_run, tick, obs, act, rew, logits, log_prob,
-      is_fir_out, hx, cx, ep_ret, F_env, env_msg, A, seed, time_horizon,
-      max_episode_steps);
-  switch (env_id) {
-    case 0: launch_env<CartPoleDyn>(a, (int)body_w.size(1)); break;
-  }
+  with_discrete_env(env_id, [&](auto env, const char* env_msg) {
+    using Policy = CategoricalSample<decltype(env)>;
+    const RolloutArgs a = pack_rollout_args(
+        body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, env_state, h, c,
+        is_fir, ep_steps, ep_run, tick, obs, act, rew, logits, log_prob,
+        is_fir_out, hx, cx, ep_ret, Policy::Env::kObsDim, env_msg,
+        Policy::kHeads, seed, time_horizon, max_episode_steps);
+    launch_train<Policy>(a, (int)body_w.size(1));
+  });
 }
 
-// Gaussian-policy sibling. env_id: 1 = MountainCarContinuous-v0. mode: 0 =
-// heads (mu, std), PPO-C sampling; 1 = heads (mu, log_std), SAC-C sampling
-// with optional OU exploration (ou_envs, warmup_steps; see GaussianArgs).
+// Gaussian-policy sibling. env_id: see with_continuous_env. mode: 0 = heads
+// (mu, std), PPO-C sampling; 1 = heads (mu, log_std), SAC-C sampling with
+// optional OU exploration (ou_envs, warmup_steps; see GaussianArgs).
 void rollout_gaussian_hip(
     const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
     const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
@@ -1267,86 +1199,78 @@ void rollout_gaussian_hip(
     at::Tensor& cx, at::Tensor& ep_ret, long env_id, long mode, long seed,
     long time_horizon, long max_episode_steps, long ou_envs,
     long warmup_steps, double ou_theta, double ou_sigma) {
-  long F_env = 0;
-  const char* env_msg = "";
-  switch (env_id) {
-    case 1:
-      F_env = MountainCarContDyn::kObsDim;
-      env_msg = "MountainCarContinuous needs obs_dim 2";
-      break;
-    default:
-      TORCH_CHECK(false, "rollout: unknown continuous device env id ", env_id);
-  }
-  TORCH_CHECK(mode == 0 || mode == 1, "rollout: mode must be 0 or 1");
-  TORCH_CHECK(ou_envs >= 0 && warmup_steps >= 0,
-              "rollout: ou_envs and warmup_steps must not be negative");
-  TORCH_CHECK(mode == 1 || (ou_envs == 0 && warmup_steps == 0),
-              "rollout: OU exploration needs mode 1 (mu, log_std)");
-  // logits field = [mu | std or log_std]: two head columns
-  GaussianArgs a;
-  static_cast<RolloutArgs&>(a) = pack_rollout_args(
-      body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, env_state, h, c,
-      is_fir, ep_steps, ep_run, tick, obs, act, rew, logits, log_prob,
-      is_fir_out, hx, cx, ep_ret, F_env, env_msg, 2, seed, time_horizon,
-      max_episode_steps);
-  TORCH_CHECK(a.D >= 2, "heads_w shape");
-  check_f32(ou_state, a.N, "ou_state");
-  TORCH_CHECK(ou_state.device() == body_w.device(),
-              "rollout: tensors on different devices");
-  a.ou_state = ou_state.data_ptr<float>();
-  a.ou_envs = (int)std::min<long>(ou_envs, INT32_MAX);
-  a.warmup_steps = (unsigned)std::min<long>(warmup_steps, UINT32_MAX);
-  a.ou_theta = (float)ou_theta;
-  a.ou_sigma = (float)ou_sigma;
-  switch (env_id) {
-    case 1:
-      launch_gaussian<MountainCarContDyn>(a, (int)body_w.size(1), (int)mode);
-      break;
-  }
+  with_continuous_env(env_id, [&](auto env, const char* env_msg) {
+    using Env = decltype(env);
+    TORCH_CHECK(mode == 0 || mode == 1, "rollout: mode must be 0 or 1");
+    TORCH_CHECK(ou_envs >= 0 && warmup_steps >= 0,
+                "rollout: ou_envs and warmup_steps must not be negative");
+    TORCH_CHECK(mode == 1 || (ou_envs == 0 && warmup_steps == 0),
+                "rollout: OU exploration needs mode 1 (mu, log_std)");
+    // logits field = [mu | std or log_std]: two head columns
+    GaussianArgs a;
+    static_cast<RolloutArgs&>(a) = pack_rollout_args(
+        body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, env_state, h, c,
+        is_fir, ep_steps, ep_run, tick, obs, act, rew, logits, log_prob,
+        is_fir_out, hx, cx, ep_ret, Env::kObsDim, env_msg, 2, seed,
+        time_horizon, max_episode_steps);
+    TORCH_CHECK(a.D >= 2, "heads_w shape");
+    check_f32(ou_state, a.N, "ou_state");
+    TORCH_CHECK(ou_state.device() == body_w.device(),
+                "rollout: tensors on different devices");
+    a.ou_state = ou_state.data_ptr<float>();
+    a.ou_envs = (int)std::min<long>(ou_envs, INT32_MAX);
+    a.warmup_steps = (unsigned)std::min<long>(warmup_steps, UINT32_MAX);
+    a.ou_theta = (float)ou_theta;
+    a.ou_sigma = (float)ou_sigma;
+    if (mode == 0)
+      launch_train<GaussianSample<Env, 0>>(a, (int)body_w.size(1));
+    else
+      launch_train<GaussianSample<Env, 1>>(a, (int)body_w.size(1));
+  });
 }
 
-// Greedy evaluation, discrete policy: E = ep_ret.size(1) whole episodes per
-// env in one launch. env_id as in rollout_discrete_hip.
+// Greedy evaluation: E = ep_ret.size(1) whole episodes per env in one launch.
+template <typename Policy>
+static void rollout_eval_hip(
+    const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
+    const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
+    const at::Tensor& heads_b, at::Tensor& ep_ret, at::Tensor& ep_len,
+    const c10::optional<at::Tensor>& start_state, const char* env_msg,
+    long seed, long max_episode_steps) {
+  const EvalArgs a = pack_eval_args(
+      body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, ep_ret, ep_len,
+      start_state, Policy::Env::kObsDim, env_msg, Policy::kHeads, seed,
+      max_episode_steps);
+  launch_eval<Policy>(a, (int)body_w.size(1));
+}
+
+// Discrete policy, arg-max action. env_id as in rollout_discrete_hip.
 void rollout_eval_discrete_hip(
     const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
     const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
     const at::Tensor& heads_b, at::Tensor& ep_ret, at::Tensor& ep_len,
     const c10::optional<at::Tensor>& start_state, long env_id, long seed,
     long max_episode_steps) {
-  switch (env_id) {
-    case 0: {
-      const EvalArgs a = pack_eval_args(
-          body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, ep_ret, ep_len,
-          start_state, CartPoleDyn::kObsDim, "CartPole needs obs_dim 4",
-          CartPoleDyn::kActions, seed, max_episode_steps);
-      launch_eval_discrete<CartPoleDyn>(a, (int)body_w.size(1));
-      break;
-    }
-    default:
-      TORCH_CHECK(false, "rollout: unknown device env id ", env_id);
-  }
+  with_discrete_env(env_id, [&](auto env, const char* env_msg) {
+    rollout_eval_hip<CategoricalGreedy<decltype(env)>>(
+        body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, ep_ret, ep_len,
+        start_state, env_msg, seed, max_episode_steps);
+  });
 }
 
-// Greedy evaluation, Gaussian policy: the action is tanh(mu) for both head
-// schemes, so only head column 0 is read. env_id as in rollout_gaussian_hip.
+// Gaussian policy, tanh(mu) for both head schemes. env_id as in
+// rollout_gaussian_hip.
 void rollout_eval_gaussian_hip(
     const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
     const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
     const at::Tensor& heads_b, at::Tensor& ep_ret, at::Tensor& ep_len,
     const c10::optional<at::Tensor>& start_state, long env_id, long seed,
     long max_episode_steps) {
-  switch (env_id) {
-    case 1: {
-      const EvalArgs a = pack_eval_args(
-          body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, ep_ret, ep_len,
-          start_state, MountainCarContDyn::kObsDim,
-          "MountainCarContinuous needs obs_dim 2", 1, seed, max_episode_steps);
-      launch_eval_gaussian<MountainCarContDyn>(a, (int)body_w.size(1));
-      break;
-    }
-    default:
-      TORCH_CHECK(false, "rollout: unknown continuous device env id ", env_id);
-  }
+  with_continuous_env(env_id, [&](auto env, const char* env_msg) {
+    rollout_eval_hip<GaussianGreedy<decltype(env)>>(
+        body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, ep_ret, ep_len,
+        start_state, env_msg, seed, max_episode_steps);
+  });
 }
 
 // Host evaluation of the rollout's uniform (same header as the kernel).

@@ -11,6 +11,7 @@ import torch
 from pdrl_amd.networks.models import (MlpLSTMSeperateContinuous,
                                       MlpLSTMSingleContinuous)
 from pdrl_amd.ops.rollout import DeviceRollout
+from tests.test_device_rollout_gpu import STATE, check_split_launches
 
 pytestmark = pytest.mark.gpu
 
@@ -170,6 +171,24 @@ def test_parity_thresholds_ou():
     """The threshold case with the first 32 envs (the goal runners) on OU
     exploration (figures in _check_parity)."""
     _check_parity(1, 64, 64, preset=True, ou_envs=32, min_goals=30, min_walls=30)
+
+
+@pytest.mark.parametrize("mode,explore", [
+    (0, {}),
+    # env 0 explores forever, the others until tick 8 (inside the second
+    # launch): the OU state is carried over launches and zeroed by resets
+    (1, dict(ou_envs=1, warmup_steps=8)),
+])
+def test_split_launches_equal_one_launch(mode, explore):
+    # max_episode_steps=3: six truncations per env in 20 steps, one of them
+    # on the last step of the third launch (is_fir = 1 carried over), and
+    # ep_steps 2 and 1 carried over the first two boundaries
+    core = _model(mode, 32).to(DEV).actor.core
+    check_split_launches(
+        lambda seq_len: DeviceRollout(core, ENV, 3, seq_len, DEV, 1,
+                                      time_horizon=500, max_episode_steps=3,
+                                      **explore),
+        min_episodes=18, state=STATE + ("ou_state",))
 
 
 # --------------------------------------------------------------------------- #

@@ -89,6 +89,39 @@ def test_parity_h128_streamed_weights():
     _check_parity(128, 5, seed=1, max_steps=None, min_episodes=1)
 
 
+STATE = ("env_state", "h", "c", "is_fir", "ep_steps", "ep_run", "tick")
+
+
+def check_split_launches(make, min_episodes, state=STATE):
+    """Four launches of 5 steps equal one launch of 20, bit for bit: a rollout
+    is a pure function of the per-env state that one launch hands to the
+    next, so no margin mask and no tolerance. ``make(seq_len)`` builds the
+    rollout; both get the same core and seed."""
+    split, whole = make(5), make(20)
+    assert split.eager == whole.eager == (split.device.type == "cpu")
+    chunks = [{k: v.clone() for k, v in split.rollout().items()}
+              for _ in range(4)]
+    want = whole.rollout()
+    for k in want:
+        assert torch.equal(torch.cat([c[k] for c in chunks], dim=1), want[k]), k
+    for k in state:
+        assert torch.equal(getattr(split, k), getattr(whole, k)), k
+    games, mean50 = whole.episode_stats()
+    assert games >= min_episodes  # resets inside and across the launches
+    assert split.episode_stats() == (games, mean50)
+
+
+def test_split_launches_equal_one_launch():
+    # max_episode_steps=7: every env truncates at least twice in 20 steps,
+    # with ep_steps 5, 3 and 1 (or less) carried over the three boundaries
+    torch.manual_seed(0)
+    core = MlpLSTMSingle(4, 2, S, 32).to(DEV).actor.core
+    check_split_launches(
+        lambda seq_len: DeviceRollout(core, "CartPole-v1", 3, seq_len, DEV, 1,
+                                      time_horizon=500, max_episode_steps=7),
+        min_episodes=6)
+
+
 def test_host_hash_matches_reference():
     from pdrl_amd import ops
 
