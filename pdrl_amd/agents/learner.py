@@ -16,8 +16,9 @@ MI355X-first differences:
 * batch staging goes through a pinned-host buffer + async H2D copy
   (BatchStager below) instead of per-field blocking copies;
 * device actor mode (``"actor_mode": "device"``): for envs with device
-  dynamics (CartPole-v1 with a discrete policy, MountainCarContinuous-v0
-  with a Gaussian one) the learner rolls out on the GPU itself
+  dynamics (CartPole-v1 / Acrobot-v1 with a discrete policy,
+  MountainCarContinuous-v0 / Pendulum-v1 with a Gaussian one) the learner
+  rolls out on the GPU itself
   (ops/rollout.py) and needs no ring, storage, manager or workers — see
   ``Learner._init_device_actor``. Env state is not checkpointed;
 * greedy evaluation (``"eval_interval": N``, either actor mode): every N

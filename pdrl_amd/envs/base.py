@@ -107,8 +107,9 @@ def make(env_name: str, **kwargs):
     """gym.make-equivalent: native envs first, then any gymnasium env when
     gymnasium is importable (absent in this container — the native
     CartPole/MountainCarContinuous implementations cover the reference's
-    target envs without it)."""
-    from . import cartpole, mountain_car, fake  # noqa: F401  (populate registry)
+    target envs without it; Pendulum and Acrobot are native too)."""
+    from . import (acrobot, cartpole, fake, mountain_car,  # noqa: F401
+                   pendulum)  # (populate registry)
 
     if env_name in _REGISTRY:
         return _REGISTRY[env_name](**kwargs)

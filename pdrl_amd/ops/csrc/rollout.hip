@@ -32,7 +32,8 @@
 //
 // Where things go (two places each, no kernel is touched):
 //   a new env     its traits struct, and its line in the env table of its
-//                 family right below it ("native env dynamics");
+//                 family right below it ("native env dynamics"); an env whose
+//                 observation is not its state adds kStateDim and observe();
 //   a new policy  one scheme struct in "policy schemes" (sampling schemes
 //                 feed rollout_train, greedy ones rollout_eval), and the
 //                 entry point that launches it.
@@ -64,6 +65,33 @@ constexpr float kNoEpisode = -1.0e30f;
 // and splits the update at the action instead. A second env is one more
 // struct and one more line in its family's table (with_discrete_env /
 // with_continuous_env).
+//
+// An env whose observation is not its state vector (hidden state, angles seen
+// as cos / sin) also defines kStateDim and observe(state, obs): the kernels
+// carry kStateDim values per env (env_state, start_state) and feed the policy
+// and the ``obs`` record the kObsDim values of observe. An env that defines
+// neither is an identity env: kStateDim == kObsDim, and the observation array
+// IS the state array (chosen at compile time: no extra LDS, copy or barrier).
+
+template <typename Env, typename = void>
+struct EnvObs {  // identity env
+  static constexpr bool kIdentity = true;
+  static constexpr int kStateDim = Env::kObsDim;
+};
+template <typename Env>
+struct EnvObs<Env, std::void_t<decltype(&Env::observe)>> {
+  static constexpr bool kIdentity = false;
+  static constexpr int kStateDim = Env::kStateDim;
+};
+
+// x modulo 2π into [-π, π), as x - 2π·floor((x + π) / 2π) in explicit
+// roundings on both sides (wrap_angle in pdrl_amd/ops/rollout.py): the floor
+// decides a jump of 2π, and no library remainder is called.
+__device__ __forceinline__ float wrap_angle(float x) {
+  constexpr float kPi = 3.1415927f, kTwoPi = 6.2831855f;
+  return __fsub_rn(
+      x, __fmul_rn(kTwoPi, floorf(__fdiv_rn(__fadd_rn(x, kPi), kTwoPi))));
+}
 
 // CartPole-v1: constants and Euler update of pdrl_amd/envs/cartpole.py, fp32.
 struct CartPoleDyn {
@@ -102,6 +130,72 @@ struct CartPoleDyn {
     terminated = x < -kXThreshold || x > kXThreshold ||
                  theta < -kThetaThreshold || theta > kThetaThreshold;
     reward = 1.0f;
+  }
+};
+
+// Acrobot-v1: "book" equations of motion and RK4 step of
+// pdrl_amd/envs/acrobot.py, fp32, in the op order of the oracle (AcrobotDyn in
+// pdrl_amd/ops/rollout.py) with the unit masses and lengths folded in. State
+// (θ1, θ2, θ̇1, θ̇2), observed as (cos θ1, sin θ1, cos θ2, sin θ2, θ̇1, θ̇2).
+struct AcrobotDyn {
+  static constexpr int kObsDim = 6;
+  static constexpr int kStateDim = 4;
+  static constexpr int kActions = 3;
+  static constexpr int kResetDraws = 4;
+
+  __device__ static void observe(const float* s, float* o) {
+    sincosf(s[0], &o[1], &o[0]);
+    sincosf(s[1], &o[3], &o[2]);
+    o[4] = s[2]; o[5] = s[3];
+  }
+
+  __device__ static void reset(float* s, const float* u) {
+#pragma unroll
+    for (int i = 0; i < kStateDim; ++i)
+      s[i] = __fadd_rn(-0.1f, __fmul_rn(0.2f, u[i]));
+  }
+
+  // (θ̈1, θ̈2): d1 = 3.5 + cos θ2, d2 = 1.25 + 0.5 cos θ2, cos(x - π/2) = sin x
+  __device__ __forceinline__ static void derivs(float t1, float t2, float v1,
+                                                float v2, float torque,
+                                                float& a1, float& a2) {
+    float c2, s2;
+    sincosf(t2, &s2, &c2);
+    const float d1 = 3.5f + c2;
+    const float d2 = 1.25f + 0.5f * c2;
+    const float phi2 = 4.9f * sinf(t1 + t2);
+    const float phi1 =
+        -0.5f * v2 * v2 * s2 - v2 * v1 * s2 + 14.7f * sinf(t1) + phi2;
+    a2 = (torque + d2 / d1 * phi1 - 0.5f * v1 * v1 * s2 - phi2) /
+         (1.25f - d2 * d2 / d1);
+    a1 = -(d2 * a2 + phi1) / d1;
+  }
+
+  __device__ static void step(float* s, int a, float& reward,
+                              bool& terminated) {
+    constexpr float kDt = 0.2f, kHalf = 0.1f, kSixth = 0.2 / 6.0;
+    constexpr float kMaxVel1 = 4.0 * 3.141592653589793;
+    constexpr float kMaxVel2 = 9.0 * 3.141592653589793;
+    float t1 = s[0], t2 = s[1], v1 = s[2], v2 = s[3];
+    const float torque = (float)a - 1.0f;
+    float k1a, k1b, k2a, k2b, k3a, k3b, k4a, k4b;
+    derivs(t1, t2, v1, v2, torque, k1a, k1b);
+    const float x1 = v1 + kHalf * k1a, x2 = v2 + kHalf * k1b;
+    derivs(t1 + kHalf * v1, t2 + kHalf * v2, x1, x2, torque, k2a, k2b);
+    const float y1 = v1 + kHalf * k2a, y2 = v2 + kHalf * k2b;
+    derivs(t1 + kHalf * x1, t2 + kHalf * x2, y1, y2, torque, k3a, k3b);
+    const float z1 = v1 + kDt * k3a, z2 = v2 + kDt * k3b;
+    derivs(t1 + kDt * y1, t2 + kDt * y2, z1, z2, torque, k4a, k4b);
+    t1 = wrap_angle(t1 + kSixth * (v1 + 2.0f * x1 + 2.0f * y1 + z1));
+    t2 = wrap_angle(t2 + kSixth * (v2 + 2.0f * x2 + 2.0f * y2 + z2));
+    v1 = v1 + kSixth * (k1a + 2.0f * k2a + 2.0f * k3a + k4a);
+    v2 = v2 + kSixth * (k1b + 2.0f * k2b + 2.0f * k3b + k4b);
+    v1 = fminf(fmaxf(v1, -kMaxVel1), kMaxVel1);
+    v2 = fminf(fmaxf(v2, -kMaxVel2), kMaxVel2);
+    s[0] = t1; s[1] = t2; s[2] = v1; s[3] = v2;
+    // the tip height decides the episode: explicit roundings
+    terminated = __fsub_rn(-cosf(t1), cosf(__fadd_rn(t1, t2))) > 1.0f;
+    reward = terminated ? 0.0f : -1.0f;
   }
 };
 
@@ -145,12 +239,52 @@ struct MountainCarContDyn {
   }
 };
 
+// Pendulum-v1 with the normalised action of pdrl_amd/envs/pendulum.py (torque
+// 2·clip(a, -1, 1)), fp32, in the op order of the oracle (PendulumDyn in
+// pdrl_amd/ops/rollout.py); g = 10, m = l = 1, dt = 0.05 folded in. State
+// (θ, θ̇) with θ never wrapped, observed as (cos θ, sin θ, θ̇). Nothing here
+// is discontinuous (the clips and wrap(θ)² are continuous), so apart from the
+// wrap and reset no rounding is pinned.
+struct PendulumDyn {
+  static constexpr int kObsDim = 3;
+  static constexpr int kStateDim = 2;
+  static constexpr int kActDim = 1;
+  static constexpr int kResetDraws = 2;
+
+  __device__ static void observe(const float* s, float* o) {
+    sincosf(s[0], &o[1], &o[0]);
+    o[2] = s[1];
+  }
+
+  __device__ static void reset(float* s, const float* u) {
+    s[0] = __fadd_rn(-3.1415927f, __fmul_rn(6.2831855f, u[0]));
+    s[1] = __fadd_rn(-1.0f, __fmul_rn(2.0f, u[1]));
+  }
+
+  // 15·sin θ·dt
+  __device__ static float drift(const float* s) { return 0.75f * sinf(s[0]); }
+
+  __device__ static void step(float* s, float a, float drift, float& reward,
+                              bool& terminated) {
+    const float u = 2.0f * fminf(fmaxf(a, -1.0f), 1.0f);
+    float th = s[0], thd = s[1];
+    const float w = wrap_angle(th);
+    reward = -(w * w + 0.1f * thd * thd + 0.001f * u * u);  // pre-step state
+    thd = fminf(fmaxf(thd + (drift + 0.15f * u), -8.0f), 8.0f);
+    th = th + 0.05f * thd;
+    s[0] = th;
+    s[1] = thd;
+    terminated = false;
+  }
+};
+
 // Env tables (ids are assigned in pdrl_amd/ops/rollout.py): f(traits, message
 // raised when the core's obs_dim does not match).
 template <typename Fn>
 void with_discrete_env(long env_id, Fn&& f) {
   switch (env_id) {
     case 0: f(CartPoleDyn{}, "CartPole needs obs_dim 4"); break;
+    case 2: f(AcrobotDyn{}, "Acrobot needs obs_dim 6"); break;
     default: TORCH_CHECK(false, "rollout: unknown device env id ", env_id);
   }
 }
@@ -161,6 +295,7 @@ void with_continuous_env(long env_id, Fn&& f) {
     case 1:
       f(MountainCarContDyn{}, "MountainCarContinuous needs obs_dim 2");
       break;
+    case 3: f(PendulumDyn{}, "Pendulum needs obs_dim 3"); break;
     default:
       TORCH_CHECK(false, "rollout: unknown continuous device env id ", env_id);
   }
@@ -180,7 +315,7 @@ struct PolicyWeights {
 
 struct RolloutArgs : PolicyWeights {
   // persistent per-env state (read and written)
-  float* env_state;      // (N, F)
+  float* env_state;      // (N, kStateDim)
   float* h;              // (N, H)
   float* c;              // (N, H)
   float* is_fir;         // (N)
@@ -353,7 +488,7 @@ struct GaussianArgs : RolloutArgs {
 
 // Arguments of rollout_eval (see there).
 struct EvalArgs : PolicyWeights {
-  const float* start_state;  // (N, F) start of episode 0, or nullptr
+  const float* start_state;  // (N, kStateDim) start of episode 0, or nullptr
   float* ep_ret;             // (N, E)
   int* ep_len;               // (N, E)
   int N, E, D;
@@ -366,18 +501,61 @@ constexpr int kEvalGoOn = 0, kEvalNextEpisode = 1, kEvalAllDone = 2;
 
 // ---- LDS and step parts shared by both kernels -----------------------------
 // The LDS block of a kernel: the recurrent part (b128 broadcast reads, hence
-// the alignment), the K leading head columns ([a][k]), the env state and the
+// the alignment), the K leading head columns ([a][k]), the env's observation
+// (FE = kObsDim values; an env with its own observe() keeps its kStateDim
+// state values behind them, FE = kObsDim + kStateDim: env_state_lds) and the
 // reset uniforms of the step. Separate arrays on purpose: as members of one
 // struct they cost the Gaussian rollout about 1 % (the compiler lays out and
 // addresses separate arrays better; profiles/device_rollout.md).
-#define PDRL_ROLLOUT_LDS(H, F, K, R)                              \
+#define PDRL_ROLLOUT_LDS(H, FE, K, R)                             \
   __shared__ __attribute__((aligned(16))) float s_xb[H];         \
   __shared__ __attribute__((aligned(16))) float s_h[H];          \
   __shared__ __attribute__((aligned(16))) float s_c[H];          \
   __shared__ __attribute__((aligned(16))) float s_gates[4 * H];  \
   __shared__ float s_hw[K * H];                                  \
-  __shared__ float s_obs[F];                                     \
+  __shared__ float s_obs[FE];                                    \
   __shared__ float s_ur[R]
+
+template <typename Env>
+constexpr int kEnvLdsFloats =
+    Env::kObsDim + (EnvObs<Env>::kIdentity ? 0 : EnvObs<Env>::kStateDim);
+
+// Where the env's state lives: in the observation array itself (identity
+// env) or right behind it.
+template <typename Env>
+__device__ __forceinline__ float* env_state_lds(float* s_obs) {
+  if constexpr (EnvObs<Env>::kIdentity)
+    return s_obs;
+  else
+    return s_obs + Env::kObsDim;
+}
+
+// Thread 0, start of a launch: the first state into LDS and, where the env
+// has its own observe(), its observation.
+template <typename Env>
+__device__ __forceinline__ void publish_state(const float* st, float* s_obs,
+                                              float* s_state) {
+  constexpr int SD = EnvObs<Env>::kStateDim;
+#pragma unroll
+  for (int k = 0; k < SD; ++k) s_state[k] = st[k];
+  if constexpr (!EnvObs<Env>::kIdentity) {
+    float ob[Env::kObsDim];
+    Env::observe(st, ob);
+#pragma unroll
+    for (int k = 0; k < Env::kObsDim; ++k) s_obs[k] = ob[k];
+  }
+}
+
+// Envs with their own observe() fill the scalar register file: the trig
+// expansions come on top of the 23 argument pointers of a training launch,
+// and the addresses the epilogue writes through, live over the whole step
+// loop, are then spilt to VGPR lanes. Such an instance keeps the address of
+// a persistent scalar in two VGPRs instead (kHold; otherwise nothing
+// happens and the instance is what it was).
+template <bool kHold, typename T>
+__device__ __forceinline__ void hold_in_vgprs(T*& ptr) {
+  if constexpr (kHold) asm volatile("" : "+v"(ptr));
+}
 
 // Head biases into registers (every thread), head columns into LDS.
 template <int H, int K>
@@ -437,19 +615,23 @@ __device__ __forceinline__ void draw_reset_uniform(int k, float* s_ur,
 //   Env, kHeads   the env traits; the number of leading head columns read
 //   Lds           its private LDS, written by side(), read by post()
 //   Choice        what thread 0 carries over the fourth barrier
-//   side(lane, s_obs, lds, s_ur, seed, n, ctr)
+//   side(lane, s_state, lds, s_ur, seed, n, ctr)
 //                 wave 1 (lane = tid - kWave) while wave 0 reduces the heads:
 //                 dynamics that need no action yet, random draws, and the
 //                 uniforms of a reset caused by this step (hash counter ctr)
+//   next_obs(ch, lds, fresh, st, ob)
+//                 thread 0, envs with their own observe() only: the
+//                 observation of the step's final state (``fresh``: a reset
+//                 has replaced what post() yielded)
 // A sampling scheme (rollout_train) also has Args, Regs (thread-0 registers
 // carried over the steps and, through load / store, over the launches) and
 //   pre(p, row, n, tick, lg, ch)      thread 0, before the barrier: what
 //                 needs the heads only; records ``logits``
-//   post(p, row, n, tick, ch, regs, lds, s_obs, st, reward, terminated)
+//   post(p, row, n, tick, ch, regs, lds, s_state, st, reward, terminated)
 //                 thread 0, after it: records ``act`` and ``log_prob`` (or
 //                 pre did), yields the step's outcome
 // and a greedy scheme (rollout_eval), which records nothing,
-//   pre(lg, ch) and post(ch, lds, s_obs, st, reward, terminated).
+//   pre(lg, ch) and post(ch, lds, s_state, st, reward, terminated).
 // The precise libm forms throughout: parity of the sample against the oracle
 // is what the tests measure.
 
@@ -465,35 +647,55 @@ struct NoRegs {
 // EVERY action (lane = action) and draws the reset uniforms, so thread 0's
 // scalar chain (softmax / sample / log-prob, or the arg-max) and the env's
 // (sin / cos / divides) run side by side; post only picks a candidate.
+// Its LDS: the candidates of one step. An env with its own observe() also
+// keeps every candidate's observation, so that picking stays a copy.
+template <int A, int SD, int F, bool kIdentity>
+struct CandidateLds {
+  alignas(16) float cand[A * SD];  // next state for every action
+  float crew[A];
+  int cterm[A];
+};
+template <int A, int SD, int F>
+struct CandidateLds<A, SD, F, false> {
+  alignas(16) float cand[A * SD];
+  float cobs[A * F];  // its observation
+  float crew[A];
+  int cterm[A];
+};
+
 template <typename EnvT>
 struct CategoricalBase {
   using Env = EnvT;
   static constexpr int F = Env::kObsDim;
+  static constexpr int SD = EnvObs<Env>::kStateDim;
+  static constexpr bool kIdentity = EnvObs<Env>::kIdentity;
   static constexpr int A = Env::kActions;
   static constexpr int kHeads = A;
 
-  struct Lds {
-    alignas(16) float cand[A * F];  // next state for every action
-    float crew[A];
-    int cterm[A];
-  };
+  using Lds = CandidateLds<A, SD, F, kIdentity>;
   struct Choice {
     int chosen = 0;
   };
 
-  __device__ __forceinline__ static void side(int lane, const float* s_obs,
+  __device__ __forceinline__ static void side(int lane, const float* s_state,
                                               Lds& s, float* s_ur,
                                               unsigned seed, int n,
                                               unsigned ctr) {
     if (lane < A) {
-      float st[F];
+      float st[SD];
 #pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+      for (int k = 0; k < SD; ++k) st[k] = s_state[k];
       float reward;
       bool terminated;
       Env::step(st, lane, reward, terminated);
 #pragma unroll
-      for (int k = 0; k < F; ++k) s.cand[lane * F + k] = st[k];
+      for (int k = 0; k < SD; ++k) s.cand[lane * SD + k] = st[k];
+      if constexpr (!kIdentity) {
+        float ob[F];
+        Env::observe(st, ob);
+#pragma unroll
+        for (int k = 0; k < F; ++k) s.cobs[lane * F + k] = ob[k];
+      }
       s.crew[lane] = reward;
       s.cterm[lane] = terminated ? 1 : 0;
     } else {
@@ -507,9 +709,25 @@ struct CategoricalBase {
                                               float& reward,
                                               bool& terminated) {
 #pragma unroll
-    for (int k = 0; k < F; ++k) st[k] = s.cand[ch.chosen * F + k];
+    for (int k = 0; k < SD; ++k) st[k] = s.cand[ch.chosen * SD + k];
     reward = s.crew[ch.chosen];
     terminated = s.cterm[ch.chosen] != 0;
+  }
+
+  // Observation of the step's final state ``st`` (envs with their own
+  // observe()): the chosen candidate's, unless a reset replaced the state
+  // (rare), which is observed here.
+  __device__ __forceinline__ static void next_obs(const Choice& ch,
+                                                  const Lds& s, bool fresh,
+                                                  const float* st, float* ob) {
+    if constexpr (!kIdentity) {
+      if (fresh) {
+        Env::observe(st, ob);
+      } else {
+#pragma unroll
+        for (int k = 0; k < F; ++k) ob[k] = s.cobs[ch.chosen * F + k];
+      }
+    }
   }
 };
 
@@ -596,33 +814,45 @@ struct CategoricalGreedy : CategoricalBase<EnvT> {
 template <typename EnvT>
 struct GaussianBase {
   using Env = EnvT;
-  static constexpr int F = Env::kObsDim;
+  static constexpr int SD = EnvObs<Env>::kStateDim;
   // One tick has eight hash lanes: 1..4 reset, 5 / 6 the normal. A second
   // action dimension needs a wider counter (rollout_rng.h).
   static_assert(Env::kActDim == 1,
                 "eight hash lanes per tick allow exactly one action dimension");
 
-  __device__ __forceinline__ static void env_side(int lane, const float* s_obs,
+  __device__ __forceinline__ static void env_side(int lane,
+                                                  const float* s_state,
                                                   float& s_drift, float* s_ur,
                                                   unsigned seed, int n,
                                                   unsigned ctr) {
     if (lane == 0) {
-      float st[F];
+      float st[SD];
 #pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+      for (int k = 0; k < SD; ++k) st[k] = s_state[k];
       s_drift = Env::drift(st);
     } else {
       draw_reset_uniform<Env::kResetDraws>(lane - 1, s_ur, seed, n, ctr);
     }
   }
 
-  __device__ __forceinline__ static void env_step(const float* s_obs,
+  __device__ __forceinline__ static void env_step(const float* s_state,
                                                   float act, float drift,
                                                   float* st, float& reward,
                                                   bool& terminated) {
 #pragma unroll
-    for (int k = 0; k < F; ++k) st[k] = s_obs[k];
+    for (int k = 0; k < SD; ++k) st[k] = s_state[k];
     Env::step(st, act, drift, reward, terminated);
+  }
+
+  // Thread 0 stepped the one chosen action, so it observes the outcome too
+  // (envs with their own observe()). Observing in the body threads at the
+  // top of the next step instead measured 29-32 % slower
+  // (profiles/device_rollout.md).
+  template <typename Choice, typename Lds>
+  __device__ __forceinline__ static void next_obs(const Choice&, const Lds&,
+                                                  bool, const float* st,
+                                                  float* ob) {
+    if constexpr (!EnvObs<Env>::kIdentity) Env::observe(st, ob);
   }
 };
 
@@ -646,17 +876,28 @@ struct GaussianSample : GaussianBase<EnvT> {
     float loc = 0.0f, sd = 0.0f, ls = 0.0f;
   };
   struct Regs {  // the OU exploration state (Mode 1)
+    static constexpr bool kHold = !EnvObs<EnvT>::kIdentity;
     float ou = 0.0f;
+    float* ou_ptr = nullptr;  // kHold only: see hold_in_vgprs
     __device__ __forceinline__ void load(const Args& p, int n) {
-      if constexpr (Mode == 1) ou = p.ou_state[n];
+      if constexpr (Mode == 1 && kHold) {
+        ou_ptr = p.ou_state + n;
+        hold_in_vgprs<true>(ou_ptr);
+        ou = *ou_ptr;
+      } else if constexpr (Mode == 1) {
+        ou = p.ou_state[n];
+      }
     }
     __device__ __forceinline__ void store(const Args& p, int n) const {
-      if constexpr (Mode == 1) p.ou_state[n] = ou;
+      if constexpr (Mode == 1 && kHold)
+        *ou_ptr = ou;
+      else if constexpr (Mode == 1)
+        p.ou_state[n] = ou;
     }
     __device__ __forceinline__ void reset() { ou = 0.0f; }
   };
 
-  __device__ __forceinline__ static void side(int lane, const float* s_obs,
+  __device__ __forceinline__ static void side(int lane, const float* s_state,
                                               Lds& s, float* s_ur,
                                               unsigned seed, int n,
                                               unsigned ctr) {
@@ -668,7 +909,7 @@ struct GaussianSample : GaussianBase<EnvT> {
       s.normal = __fmul_rn(sqrtf(__fmul_rn(-2.0f, logf(1.0f - u5))),
                            cosf(__fmul_rn(6.2831855f, u6)));
     } else {
-      Base::env_side(lane - 1, s_obs, s.drift, s_ur, seed, n, ctr);
+      Base::env_side(lane - 1, s_state, s.drift, s_ur, seed, n, ctr);
     }
   }
 
@@ -695,7 +936,7 @@ struct GaussianSample : GaussianBase<EnvT> {
   __device__ __forceinline__ static void post(const Args& p, long row, int n,
                                               unsigned tick, const Choice& ch,
                                               Regs& regs, const Lds& s,
-                                              const float* s_obs, float* st,
+                                              const float* s_state, float* st,
                                               float& reward,
                                               bool& terminated) {
     const float nrm = s.normal;
@@ -729,7 +970,7 @@ struct GaussianSample : GaussianBase<EnvT> {
     }
     p.act[row] = act;
     p.log_prob[row] = lp;
-    Base::env_step(s_obs, act, s.drift, st, reward, terminated);
+    Base::env_step(s_state, act, s.drift, st, reward, terminated);
   }
 };
 
@@ -747,11 +988,11 @@ struct GaussianGreedy : GaussianBase<EnvT> {
     float act = 0.0f;
   };
 
-  __device__ __forceinline__ static void side(int lane, const float* s_obs,
+  __device__ __forceinline__ static void side(int lane, const float* s_state,
                                               Lds& s, float* s_ur,
                                               unsigned seed, int n,
                                               unsigned ctr) {
-    Base::env_side(lane, s_obs, s.drift, s_ur, seed, n, ctr);
+    Base::env_side(lane, s_state, s.drift, s_ur, seed, n, ctr);
   }
 
   __device__ __forceinline__ static void pre(const float (&lg)[1],
@@ -760,10 +1001,10 @@ struct GaussianGreedy : GaussianBase<EnvT> {
   }
 
   __device__ __forceinline__ static void post(const Choice& ch, const Lds& s,
-                                              const float* s_obs, float* st,
+                                              const float* s_state, float* st,
                                               float& reward,
                                               bool& terminated) {
-    Base::env_step(s_obs, ch.act, s.drift, st, reward, terminated);
+    Base::env_step(s_state, ch.act, s.drift, st, reward, terminated);
   }
 };
 
@@ -773,6 +1014,9 @@ __global__ __launch_bounds__(4 * H) void rollout_train(
     typename Policy::Args p) {
   using Env = typename Policy::Env;
   constexpr int F = Env::kObsDim;
+  constexpr int SD = EnvObs<Env>::kStateDim;
+  constexpr bool kIdentity = EnvObs<Env>::kIdentity;
+  static_assert(!kIdentity || SD == F, "identity env: the obs is the state");
   constexpr int K = Policy::kHeads;
   constexpr int R = Env::kResetDraws;
   static_assert(R >= 1 && R <= 4, "reset draws use hash lanes 1..4");
@@ -780,7 +1024,8 @@ __global__ __launch_bounds__(4 * H) void rollout_train(
   const int n = blockIdx.x;
   if (n >= p.N) return;  // uniform per workgroup
 
-  PDRL_ROLLOUT_LDS(H, F, K, R);
+  PDRL_ROLLOUT_LDS(H, kEnvLdsFloats<Env>, K, R);
+  float* const s_state = env_state_lds<Env>(s_obs);
   __shared__ typename Policy::Lds sp;
   __shared__ float s_fir;
   __shared__ int s_reset;
@@ -789,14 +1034,24 @@ __global__ __launch_bounds__(4 * H) void rollout_train(
   core.load(p, tid, n, s_h, s_c);
   float hb[K];
   stage_heads<H, K>(p, p.D, tid, s_hw, hb);
-  if (tid < F) s_obs[tid] = p.env_state[(long)n * F + tid];
+  if constexpr (kIdentity) {
+    if (tid < F) s_obs[tid] = p.env_state[(long)n * F + tid];
+  } else if (tid == 0) {
+    float st[SD];
+#pragma unroll
+    for (int k = 0; k < SD; ++k) st[k] = p.env_state[(long)n * SD + k];
+    publish_state<Env>(st, s_obs, s_state);
+  }
 
   // episode bookkeeping and the scheme's registers live in thread 0 across
   // the S steps
   int steps = 0;
   float run = 0.0f;
   typename Policy::Regs regs;
-  unsigned tick = p.tick[n];  // every thread tracks it (hash counter)
+  // every thread tracks the tick (hash counter)
+  unsigned* tick_ptr = p.tick + n;
+  hold_in_vgprs<!kIdentity>(tick_ptr);
+  unsigned tick = *tick_ptr;
   if (tid == 0) {
     s_fir = p.is_fir[n];
     steps = p.ep_steps[n];
@@ -815,7 +1070,7 @@ __global__ __launch_bounds__(4 * H) void rollout_train(
     if (tid < kWave)
       reduce_heads<H, K>(s_h, s_hw, hb, tid, lg);
     else
-      Policy::side(tid - kWave, s_obs, sp, s_ur, p.seed, n, tick);
+      Policy::side(tid - kWave, s_state, sp, s_ur, p.seed, n, tick);
     // thread 0 already holds the reduced heads: no barrier needed
     typename Policy::Choice ch;
     if (tid == 0) Policy::pre(p, row, n, tick, lg, ch);
@@ -823,10 +1078,10 @@ __global__ __launch_bounds__(4 * H) void rollout_train(
 
     // the step's outcome; termination, auto-reset (thread 0)
     if (tid == 0) {
-      float st[F];
+      float st[SD];
       float reward;
       bool terminated;
-      Policy::post(p, row, n, tick, ch, regs, sp, s_obs, st, reward,
+      Policy::post(p, row, n, tick, ch, regs, sp, s_state, st, reward,
                    terminated);
       steps += 1;
       run += reward;
@@ -841,7 +1096,13 @@ __global__ __launch_bounds__(4 * H) void rollout_train(
         regs.reset();
       }
 #pragma unroll
-      for (int k = 0; k < F; ++k) s_obs[k] = st[k];
+      for (int k = 0; k < SD; ++k) s_state[k] = st[k];
+      if constexpr (!kIdentity) {
+        float ob[F];
+        Policy::next_obs(ch, sp, reset, st, ob);
+#pragma unroll
+        for (int k = 0; k < F; ++k) s_obs[k] = ob[k];
+      }
       s_fir = reset ? 1.0f : 0.0f;
       s_reset = reset ? 1 : 0;
     }
@@ -854,12 +1115,12 @@ __global__ __launch_bounds__(4 * H) void rollout_train(
     p.h[(long)n * H + tid] = s_h[tid];
     p.c[(long)n * H + tid] = s_c[tid];
   }
-  if (tid < F) p.env_state[(long)n * F + tid] = s_obs[tid];
+  if (tid < SD) p.env_state[(long)n * SD + tid] = s_state[tid];
   if (tid == 0) {
     p.is_fir[n] = s_fir;
     p.ep_steps[n] = steps;
     p.ep_run[n] = run;
-    p.tick[n] = tick;
+    *tick_ptr = tick;
     regs.store(p, n);
   }
 }
@@ -882,6 +1143,9 @@ template <int H, typename Policy>
 __global__ __launch_bounds__(4 * H) void rollout_eval(EvalArgs p) {
   using Env = typename Policy::Env;
   constexpr int F = Env::kObsDim;
+  constexpr int SD = EnvObs<Env>::kStateDim;
+  constexpr bool kIdentity = EnvObs<Env>::kIdentity;
+  static_assert(!kIdentity || SD == F, "identity env: the obs is the state");
   constexpr int K = Policy::kHeads;
   constexpr int R = Env::kResetDraws;
   static_assert(R >= 1 && R <= 4, "reset draws use hash lanes 1..4");
@@ -889,7 +1153,9 @@ __global__ __launch_bounds__(4 * H) void rollout_eval(EvalArgs p) {
   const int n = blockIdx.x;
   if (n >= p.N) return;  // uniform per workgroup
 
-  PDRL_ROLLOUT_LDS(H, F, K, R);  // s_ur: start state of the next episode
+  // s_ur: start state of the next episode
+  PDRL_ROLLOUT_LDS(H, kEnvLdsFloats<Env>, K, R);
+  float* const s_state = env_state_lds<Env>(s_obs);
   __shared__ typename Policy::Lds sp;
   __shared__ int s_ctl;
 
@@ -899,10 +1165,10 @@ __global__ __launch_bounds__(4 * H) void rollout_eval(EvalArgs p) {
   stage_heads<H, K>(p, p.D, tid, s_hw, hb);
   zero_recurrent<H>(tid, s_h, s_c);
   if (tid == 0) {
-    float st[F];
+    float st[SD];
     if (p.start_state != nullptr) {
 #pragma unroll
-      for (int k = 0; k < F; ++k) st[k] = p.start_state[(long)n * F + k];
+      for (int k = 0; k < SD; ++k) st[k] = p.start_state[(long)n * SD + k];
     } else {
       float u[R];
 #pragma unroll
@@ -910,8 +1176,7 @@ __global__ __launch_bounds__(4 * H) void rollout_eval(EvalArgs p) {
         u[k] = pdrl_rng::uniform(p.seed, (unsigned)n, 0u, (unsigned)k + 1u);
       Env::reset(st, u);
     }
-#pragma unroll
-    for (int k = 0; k < F; ++k) s_obs[k] = st[k];
+    publish_state<Env>(st, s_obs, s_state);
   }
   __syncthreads();
 
@@ -927,7 +1192,7 @@ __global__ __launch_bounds__(4 * H) void rollout_eval(EvalArgs p) {
     if (tid < kWave)
       reduce_heads<H, K>(s_h, s_hw, hb, tid, lg);
     else
-      Policy::side(tid - kWave, s_obs, sp, s_ur, p.seed, n,
+      Policy::side(tid - kWave, s_state, sp, s_ur, p.seed, n,
                    (unsigned)episode + 1u);
     typename Policy::Choice ch;
     if (tid == 0) Policy::pre(lg, ch);
@@ -935,10 +1200,10 @@ __global__ __launch_bounds__(4 * H) void rollout_eval(EvalArgs p) {
 
     // the step's outcome; episode end and fresh start (thread 0)
     if (tid == 0) {
-      float st[F];
+      float st[SD];
       float reward;
       bool terminated;
-      Policy::post(ch, sp, s_obs, st, reward, terminated);
+      Policy::post(ch, sp, s_state, st, reward, terminated);
       steps += 1;
       run += reward;
       const bool done = terminated || steps >= p.max_episode_steps;
@@ -952,7 +1217,13 @@ __global__ __launch_bounds__(4 * H) void rollout_eval(EvalArgs p) {
         ctl = (episode + 1 >= p.E) ? kEvalAllDone : kEvalNextEpisode;
       }
 #pragma unroll
-      for (int k = 0; k < F; ++k) s_obs[k] = st[k];
+      for (int k = 0; k < SD; ++k) s_state[k] = st[k];
+      if constexpr (!kIdentity) {
+        float ob[F];
+        Policy::next_obs(ch, sp, done, st, ob);
+#pragma unroll
+        for (int k = 0; k < F; ++k) s_obs[k] = ob[k];
+      }
       s_ctl = ctl;
     }
     __syncthreads();
@@ -1046,7 +1317,8 @@ PolicyWeights pack_policy_weights(
 }
 
 // Argument checks and pointer packing shared by both training entry points;
-// A is also the width of the ``logits`` field.
+// A is also the width of the ``logits`` field. The env fixes the core's
+// obs_dim (F_env) and, on its own, the width of env_state (SD_env).
 RolloutArgs pack_rollout_args(
     const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
     const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
@@ -1055,17 +1327,19 @@ RolloutArgs pack_rollout_args(
     at::Tensor& ep_run, at::Tensor& tick, at::Tensor& obs, at::Tensor& act,
     at::Tensor& rew, at::Tensor& logits, at::Tensor& log_prob,
     at::Tensor& is_fir_out, at::Tensor& hx, at::Tensor& cx,
-    at::Tensor& ep_ret, long F_env, const char* env_msg, long A, long seed,
-    long time_horizon, long max_episode_steps) {
+    at::Tensor& ep_ret, long F_env, const char* env_msg, long SD_env, long A,
+    long seed, long time_horizon, long max_episode_steps) {
   RolloutArgs a;
   static_cast<PolicyWeights&>(a) = pack_policy_weights(
       body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, F_env, env_msg, A);
-  TORCH_CHECK(env_state.dim() == 2 && obs.dim() == 3,
-              "rollout: bad tensor ranks");
+  TORCH_CHECK(obs.dim() == 3, "rollout: bad tensor ranks");
+  TORCH_CHECK(env_state.dim() == 2 && env_state.size(1) == SD_env,
+              "rollout: env_state must be (N, ", SD_env,
+              "), the env's state vector, got ", env_state.sizes());
   const long F = body_w.size(0), H = body_w.size(1), D = heads_w.size(1);
   const long N = env_state.size(0), S = obs.size(1);
   TORCH_CHECK(N >= 1 && S >= 1, "rollout: empty batch");
-  check_f32(env_state, N * F, "env_state");
+  check_f32(env_state, N * SD_env, "env_state");
   check_f32(h, N * H, "h");
   check_f32(c, N * H, "c");
   check_f32(is_fir, N, "is_fir state");
@@ -1124,7 +1398,8 @@ EvalArgs pack_eval_args(
     const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
     const at::Tensor& heads_b, at::Tensor& ep_ret, at::Tensor& ep_len,
     const c10::optional<at::Tensor>& start_state, long F_env,
-    const char* env_msg, long A, long seed, long max_episode_steps) {
+    const char* env_msg, long SD_env, long A, long seed,
+    long max_episode_steps) {
   EvalArgs a;
   static_cast<PolicyWeights&>(a) = pack_policy_weights(
       body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, F_env, env_msg, A);
@@ -1146,7 +1421,10 @@ EvalArgs pack_eval_args(
               "rollout: tensors on different devices");
   a.start_state = nullptr;
   if (start_state.has_value()) {
-    check_f32(*start_state, N * F_env, "start_state");
+    TORCH_CHECK(start_state->dim() == 2 && start_state->size(1) == SD_env,
+                "rollout_eval: start_state must be (N, ", SD_env,
+                "), the env's state vector");
+    check_f32(*start_state, N * SD_env, "start_state");
     TORCH_CHECK(start_state->device() == dev,
                 "rollout: tensors on different devices");
     a.start_state = start_state->data_ptr<float>();
@@ -1180,7 +1458,8 @@ void rollout_discrete_hip(
         body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, env_state, h, c,
         is_fir, ep_steps, ep_run, tick, obs, act, rew, logits, log_prob,
         is_fir_out, hx, cx, ep_ret, Policy::Env::kObsDim, env_msg,
-        Policy::kHeads, seed, time_horizon, max_episode_steps);
+        EnvObs<typename Policy::Env>::kStateDim, Policy::kHeads, seed,
+        time_horizon, max_episode_steps);
     launch_train<Policy>(a, (int)body_w.size(1));
   });
 }
@@ -1211,8 +1490,8 @@ void rollout_gaussian_hip(
     static_cast<RolloutArgs&>(a) = pack_rollout_args(
         body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, env_state, h, c,
         is_fir, ep_steps, ep_run, tick, obs, act, rew, logits, log_prob,
-        is_fir_out, hx, cx, ep_ret, Env::kObsDim, env_msg, 2, seed,
-        time_horizon, max_episode_steps);
+        is_fir_out, hx, cx, ep_ret, Env::kObsDim, env_msg,
+        EnvObs<Env>::kStateDim, 2, seed, time_horizon, max_episode_steps);
     TORCH_CHECK(a.D >= 2, "heads_w shape");
     check_f32(ou_state, a.N, "ou_state");
     TORCH_CHECK(ou_state.device() == body_w.device(),
@@ -1239,7 +1518,8 @@ static void rollout_eval_hip(
     long seed, long max_episode_steps) {
   const EvalArgs a = pack_eval_args(
       body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, ep_ret, ep_len,
-      start_state, Policy::Env::kObsDim, env_msg, Policy::kHeads, seed,
+      start_state, Policy::Env::kObsDim, env_msg,
+      EnvObs<typename Policy::Env>::kStateDim, Policy::kHeads, seed,
       max_episode_steps);
   launch_eval<Policy>(a, (int)body_w.size(1));
 }

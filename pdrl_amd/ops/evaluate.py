@@ -22,7 +22,9 @@ It is the training rollout (ops/rollout.py) minus everything a batch needs:
                training ``DeviceRollout`` (envs, ticks, replay) is touched
 
 ``evaluate(start_state)`` may replace the start of episode 0 by a given
-``(N, obs_dim)`` state.
+``(N, state_dim)`` state (the env's state vector, which
+``Dyn.observe`` turns into the policy's observation; for CartPole and
+MountainCar the two are the same).
 """
 from __future__ import annotations
 
@@ -99,21 +101,21 @@ class DeviceEvaluator:
     # ------------------------------------------------------------------ #
     def _reset_uniforms(self, tick) -> torch.Tensor:
         """(N, draws) uniforms of the start state of episode ``tick``."""
-        draws = getattr(self.dyn, "reset_draws", self.dyn.obs_dim)
+        draws = getattr(self.dyn, "reset_draws", self.dyn.state_dim)
         return torch.stack([uniform(self.seed, self._env_ids, tick, k)
                             for k in range(1, draws + 1)], 1)
 
     def start_states(self, episode: int = 0) -> torch.Tensor:
-        """(N, obs_dim) start states of ``episode`` (no policy involved)."""
+        """(N, state_dim) start states of ``episode`` (no policy involved)."""
         return self.dyn.reset(self._reset_uniforms(int(episode)))
 
     @torch.no_grad()
     def evaluate(self, start_state: torch.Tensor | None = None
                  ) -> dict[str, torch.Tensor]:
         if start_state is not None and tuple(start_state.shape) != (
-                self.N, self.dyn.obs_dim):
+                self.N, self.dyn.state_dim):
             raise ValueError(
-                f"start_state must be ({self.N}, {self.dyn.obs_dim}), got "
+                f"start_state must be ({self.N}, {self.dyn.state_dim}), got "
                 f"{tuple(start_state.shape)}")
         if self.eager:
             self._evaluate_eager(start_state)
@@ -129,7 +131,8 @@ class DeviceEvaluator:
 
     def _greedy(self, state, h, c):
         """One policy step: (action, next h, next c, action margin)."""
-        outs, h, c = self.core._forward_eager(state.unsqueeze(1), h, c)
+        outs, h, c = self.core._forward_eager(
+            self.dyn.observe(state).unsqueeze(1), h, c)
         if self.continuous:
             act = torch.tanh(outs["mu"][:, 0, 0])
             return act, h, c, torch.full_like(act, float("inf"))

@@ -95,19 +95,26 @@ def uniform(seed: int, env: torch.Tensor, tick, k: int) -> torch.Tensor:
 
 # --------------------------------------------------------------------------- #
 # Reference env dynamics (fp32 torch; mirrored by the traits structs of
-# csrc/rollout.hip). A second native env is one more class here, one more
-# struct + case there.
+# csrc/rollout.hip). A further native env is one more class here, one more
+# struct + case there. Every class has ``state_dim`` and ``observe(state)``:
+# ``env_state`` is (N, state_dim), the batch's ``obs`` and the core's input
+# are ``observe(env_state)`` (obs_dim wide). For CartPole and MountainCar the
+# two are the same and ``observe`` is the identity.
 # --------------------------------------------------------------------------- #
 class CartPoleDyn:
     """CartPole-v1: constants and Euler update of envs/cartpole.py, fp32."""
 
     env_id = 0
-    obs_dim = 4
+    obs_dim = state_dim = 4
     n_actions = 2
     max_episode_steps = 500
     GRAVITY, MASS_POLE, TOTAL_MASS = 9.8, 0.1, 1.1
     LENGTH, POLE_MASS_LENGTH, FORCE_MAG, TAU = 0.5, 0.05, 10.0, 0.02
     THETA_THRESHOLD, X_THRESHOLD = 0.20943951023931953, 2.4
+
+    @staticmethod
+    def observe(state: torch.Tensor) -> torch.Tensor:
+        return state
 
     @staticmethod
     def reset(u: torch.Tensor) -> torch.Tensor:
@@ -147,12 +154,16 @@ class MountainCarContDyn:
     hash lane 1 only."""
 
     env_id = 1
-    obs_dim = 2
+    obs_dim = state_dim = 2
     act_dim = 1
     reset_draws = 1
     max_episode_steps = 999
     MIN_POSITION, MAX_POSITION, MAX_SPEED = -1.2, 0.6, 0.07
     GOAL_POSITION, GOAL_VELOCITY, POWER = 0.45, 0.0, 0.0015
+
+    @staticmethod
+    def observe(state: torch.Tensor) -> torch.Tensor:
+        return state
 
     @staticmethod
     def reset(u: torch.Tensor) -> torch.Tensor:
@@ -194,8 +205,143 @@ class MountainCarContDyn:
         return torch.where(past_goal, torch.minimum(margin, vel.abs()), margin)
 
 
+PI, TWO_PI = 3.1415927, 6.2831855  # as fp32 rounds them
+
+
+def wrap_angle(x: torch.Tensor) -> torch.Tensor:
+    """x modulo 2π into [-π, π): ``x - 2π·floor((x + π) / 2π)`` on both
+    sides, so neither calls a library remainder."""
+    return x - TWO_PI * torch.floor((x + PI) / TWO_PI)
+
+
+class AcrobotDyn:
+    """Acrobot-v1: constants, "book" equations of motion and RK4 step of
+    envs/acrobot.py, fp32, with the unit masses and lengths folded in. The
+    first env whose observation is not its state: ``state_dim`` values
+    (θ1, θ2, θ̇1, θ̇2) are carried, ``observe`` turns them into the
+    ``obs_dim`` values the policy and the batch see."""
+
+    env_id = 2
+    obs_dim = 6
+    state_dim = 4
+    n_actions = 3
+    reset_draws = 4
+    max_episode_steps = 500
+    DT = 0.2
+    MAX_VEL_1, MAX_VEL_2 = 4 * 3.141592653589793, 9 * 3.141592653589793
+
+    @staticmethod
+    def observe(state: torch.Tensor) -> torch.Tensor:
+        t1, t2, d1, d2 = state.unbind(1)
+        return torch.stack([torch.cos(t1), torch.sin(t1), torch.cos(t2),
+                            torch.sin(t2), d1, d2], 1)
+
+    @staticmethod
+    def reset(u: torch.Tensor) -> torch.Tensor:
+        """u: (N, 4) uniforms → all four in [-0.1, 0.1)."""
+        return -0.1 + 0.2 * u
+
+    @staticmethod
+    def _derivs(t1, t2, v1, v2, torque):
+        """(θ̈1, θ̈2); m1 = m2 = l1 = 1, lc = 0.5, I = 1, g = 9.8 folded in:
+        d1 = 3.5 + cos θ2, d2 = 1.25 + 0.5 cos θ2, cos(x - π/2) = sin x."""
+        c2, s2 = torch.cos(t2), torch.sin(t2)
+        d1 = 3.5 + c2
+        d2 = 1.25 + 0.5 * c2
+        phi2 = 4.9 * torch.sin(t1 + t2)
+        phi1 = -0.5 * v2 * v2 * s2 - v2 * v1 * s2 + 14.7 * torch.sin(t1) + phi2
+        a2 = ((torque + d2 / d1 * phi1 - 0.5 * v1 * v1 * s2 - phi2)
+              / (1.25 - d2 * d2 / d1))
+        a1 = -(d2 * a2 + phi1) / d1
+        return a1, a2
+
+    @staticmethod
+    def height(state: torch.Tensor) -> torch.Tensor:
+        """Tip height above the bar; the episode terminates above 1."""
+        return -torch.cos(state[:, 0]) - torch.cos(state[:, 0] + state[:, 1])
+
+    @classmethod
+    def step(cls, state: torch.Tensor, action: torch.Tensor):
+        """state (N,4) fp32, action (N,) int → (state', reward, terminated)."""
+        t1, t2, v1, v2 = state.unbind(1)
+        torque = action.to(state.dtype) - 1.0
+        dt, half = cls.DT, 0.5 * cls.DT
+        k1a, k1b = cls._derivs(t1, t2, v1, v2, torque)
+        x1, x2 = v1 + half * k1a, v2 + half * k1b
+        k2a, k2b = cls._derivs(t1 + half * v1, t2 + half * v2, x1, x2, torque)
+        y1, y2 = v1 + half * k2a, v2 + half * k2b
+        k3a, k3b = cls._derivs(t1 + half * x1, t2 + half * x2, y1, y2, torque)
+        z1, z2 = v1 + dt * k3a, v2 + dt * k3b
+        k4a, k4b = cls._derivs(t1 + dt * y1, t2 + dt * y2, z1, z2, torque)
+        sixth = dt / 6.0
+        t1 = wrap_angle(t1 + sixth * (v1 + 2.0 * x1 + 2.0 * y1 + z1))
+        t2 = wrap_angle(t2 + sixth * (v2 + 2.0 * x2 + 2.0 * y2 + z2))
+        v1 = (v1 + sixth * (k1a + 2.0 * k2a + 2.0 * k3a + k4a)).clamp(
+            -cls.MAX_VEL_1, cls.MAX_VEL_1)
+        v2 = (v2 + sixth * (k1b + 2.0 * k2b + 2.0 * k3b + k4b)).clamp(
+            -cls.MAX_VEL_2, cls.MAX_VEL_2)
+        state = torch.stack([t1, t2, v1, v2], 1)
+        terminated = cls.height(state) > 1.0
+        reward = torch.where(terminated, 0.0, -1.0).to(state.dtype)
+        return state, reward, terminated
+
+    @classmethod
+    def threshold_margin(cls, state: torch.Tensor) -> torch.Tensor:
+        """Distance of the tip height from its termination threshold. The
+        wrap needs no term: a flip moves θ by 2π, which neither the
+        observation nor the dynamics (sin / cos of θ only) can see — hence
+        ``obs``, never ``env_state``, is what two implementations share."""
+        return (cls.height(state) - 1.0).abs()
+
+
+class PendulumDyn:
+    """Pendulum-v1 with the normalised action of envs/pendulum.py (torque
+    u = 2·clip(a, -1, 1)), fp32. State (θ, θ̇) with θ never wrapped, obs
+    (cos θ, sin θ, θ̇). g = 10, m = l = 1, dt = 0.05 folded in: the
+    action-independent part of the speed update is 15·sin θ·dt."""
+
+    env_id = 3
+    obs_dim = 3
+    state_dim = 2
+    act_dim = 1
+    reset_draws = 2
+    max_episode_steps = 200
+    MAX_SPEED = 8.0
+
+    @staticmethod
+    def observe(state: torch.Tensor) -> torch.Tensor:
+        th, thd = state.unbind(1)
+        return torch.stack([torch.cos(th), torch.sin(th), thd], 1)
+
+    @staticmethod
+    def reset(u: torch.Tensor) -> torch.Tensor:
+        """u: (N, 2) uniforms → θ in [-π, π), θ̇ in [-1, 1)."""
+        return torch.stack([-PI + TWO_PI * u[:, 0], -1.0 + 2.0 * u[:, 1]], 1)
+
+    @classmethod
+    def step(cls, state: torch.Tensor, action: torch.Tensor):
+        """state (N,2) fp32, action (N,) fp32 → (state', reward, False)."""
+        th, thd = state.unbind(1)
+        u = 2.0 * action.clamp(-1.0, 1.0)
+        w = wrap_angle(th)
+        cost = w * w + 0.1 * thd * thd + 0.001 * u * u
+        drift = 0.75 * torch.sin(th)
+        thd = (thd + (drift + 0.15 * u)).clamp(-cls.MAX_SPEED, cls.MAX_SPEED)
+        th = th + 0.05 * thd
+        return (torch.stack([th, thd], 1), -cost,
+                torch.zeros_like(th, dtype=torch.bool))
+
+    @staticmethod
+    def threshold_margin(state: torch.Tensor, action: torch.Tensor) -> torch.Tensor:
+        """No discontinuity anywhere: the clips are continuous and wrap(θ)²
+        is continuous at ±π, so no env is ever excluded."""
+        return torch.full_like(state[:, 0], float("inf"))
+
+
 DEVICE_ENVS = {"CartPole-v1": CartPoleDyn,
-               "MountainCarContinuous-v0": MountainCarContDyn}
+               "MountainCarContinuous-v0": MountainCarContDyn,
+               "Acrobot-v1": AcrobotDyn,
+               "Pendulum-v1": PendulumDyn}
 # head names[:2] → sampling scheme of a Gaussian policy (as the worker chooses)
 GAUSSIAN_MODES = {("mu", "std"): 0, ("mu", "log_std"): 1}
 HALF_LOG_2PI = 0.9189385
@@ -278,7 +424,8 @@ class DeviceRollout:
             self.fields = rollout_fields(dyn.obs_dim, dyn.n_actions, H, False)
         # the batch: same tensor objects on every call (graph-capturable)
         self.batch = {k: torch.zeros(N, S, d, **f32) for k, d in self.fields.items()}
-        # persistent per-env state
+        # persistent per-env state; env_state is (N, state_dim), and the
+        # batch's obs / the core's input are dyn.observe(env_state)
         self._env_ids = torch.arange(N, device=dev, dtype=torch.int64)
         self.env_state = dyn.reset(self._reset_uniforms(0)).contiguous()
         self.ou_state = torch.zeros(N, **f32)  # OU exploration (Gaussian mode 1)
@@ -336,7 +483,7 @@ class DeviceRollout:
 
     def _reset_uniforms(self, tick) -> torch.Tensor:
         """(N, draws) uniforms of a reset caused by ``tick``: lanes 1.."""
-        draws = getattr(self.dyn, "reset_draws", self.dyn.obs_dim)
+        draws = getattr(self.dyn, "reset_draws", self.dyn.state_dim)
         return torch.stack([uniform(self.seed, self._env_ids, tick, k)
                             for k in range(1, draws + 1)], 1)
 
@@ -385,12 +532,13 @@ class DeviceRollout:
         second = self.core.head_names[1]
         for t in range(self.S):
             self.tick += 1
-            b["obs"][:, t] = self.env_state
+            obs = dyn.observe(self.env_state)
+            b["obs"][:, t] = obs
             b["hx"][:, t] = self.h
             b["cx"][:, t] = self.c
             b["is_fir"][:, t, 0] = self.is_fir
             outs, h, c = self.core._forward_eager(
-                self.env_state.unsqueeze(1), self.h, self.c)
+                obs.unsqueeze(1), self.h, self.c)
             mu, s = outs["mu"][:, 0, 0], outs[second][:, 0, 0]
             n = normal(self.seed, self._env_ids, self.tick)
             if self.mode == 0:
@@ -441,12 +589,13 @@ class DeviceRollout:
         dyn, b, A = self.dyn, self.batch, self.dyn.n_actions
         for t in range(self.S):
             self.tick += 1
-            b["obs"][:, t] = self.env_state
+            obs = dyn.observe(self.env_state)
+            b["obs"][:, t] = obs
             b["hx"][:, t] = self.h
             b["cx"][:, t] = self.c
             b["is_fir"][:, t, 0] = self.is_fir
             outs, h, c = self.core._forward_eager(
-                self.env_state.unsqueeze(1), self.h, self.c)
+                obs.unsqueeze(1), self.h, self.c)
             lg = outs["logits"][:, 0]
             # softmax → inverse CDF against one uniform (cpu_actor.cpp rule)
             mx = lg.max(dim=1).values
@@ -474,9 +623,7 @@ class DeviceRollout:
             b["log_prob"][:, t, 0] = log_prob
             ep_ret[:, t] = torch.where(reset, self.ep_run,
                                        torch.full_like(rew, NO_EPISODE))
-            fresh = dyn.reset(torch.stack(
-                [uniform(self.seed, self._env_ids, self.tick, k)
-                 for k in range(1, dyn.obs_dim + 1)], 1))
+            fresh = dyn.reset(self._reset_uniforms(self.tick))
             keep = (~reset).to(torch.float32)
             self.env_state = torch.where(reset[:, None], fresh, state)
             self.h = h * keep[:, None]

@@ -21,6 +21,9 @@ synchronize, 50 warm-up calls, timed windows of at least ``--window`` s.
 (g) rollout + replay + SAC / SAC-Continuous update in device mode at B=128
     (``Learner.next_batch`` + ``updater.step``), once per ``replay_kernel``.
     In (f) and (g) the two paths alternate inside one run.
+(h) the envs whose observation is not their state: ``rollout()`` alone at
+    N=128 and N=1024 on Acrobot-v1 and on Pendulum-v1 (both Gaussian
+    schemes), and one ``evaluate()`` call each (1 episode, N=64).
 
 ``--only-replay`` runs (f) and (g) alone.
 
@@ -255,6 +258,38 @@ def main():
                    episodes=episodes, hidden=H, env_steps=steps,
                    longest_env_steps=longest, ms_per_call=ms,
                    us_per_step=ms * 1e3 / longest, **ev.summary())
+
+    # (h) Acrobot-v1 and Pendulum-v1: rollout alone, one evaluate() call
+    acro, pen = "Acrobot-v1", "Pendulum-v1"
+    for env, mode, cls, dims in ((acro, None, MlpLSTMSingle, (6, 3)),
+                                 (pen, 0, MlpLSTMSingleContinuous, (3, 1)),
+                                 (pen, 1, MlpLSTMSeperateContinuous, (3, 1))):
+        for n_envs in (128, 1024):
+            torch.manual_seed(0)
+            model = cls(*dims, S, H).to(dev)
+            ro = DeviceRollout(model.actor.core, env, n_envs, S, dev, seed=1,
+                               time_horizon=500)
+            for _ in range(WARMUP):
+                ro.rollout()
+            vals = [timed(ro.rollout, args.window, n_envs * S, 200)
+                    for _ in range(args.repeats)]
+            report("rollout_only", vals, env=env, mode=mode, num_envs=n_envs,
+                   seq_len=S, hidden=H)
+    for env, cls, dims in ((acro, MlpLSTMSingle, (6, 3)),
+                           (pen, MlpLSTMSeperateContinuous, (3, 1))):
+        torch.manual_seed(0)
+        model = cls(*dims, S, H).to(dev)
+        ev = DeviceEvaluator(model.actor.core, env, 64, 1, dev, seed=4321)
+        for _ in range(5):
+            ev.evaluate()
+        per_env = ev.lengths.sum(1)
+        steps, longest = int(per_env.sum()), int(per_env.max())
+        vals = [timed(ev.evaluate, args.window, steps, 20)
+                for _ in range(args.repeats)]
+        ms = sorted(steps / v * 1e3 for v in vals)[len(vals) // 2]
+        report("evaluate_call", vals, env=env, num_envs=64, episodes=1,
+               hidden=H, env_steps=steps, longest_env_steps=longest,
+               ms_per_call=ms, us_per_step=ms * 1e3 / longest, **ev.summary())
 
     # (f), (g) the off-policy replay: eager ops against the fused launch
     replay_sections(args, dev, S, H)
