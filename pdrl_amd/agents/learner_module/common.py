@@ -62,6 +62,12 @@ class BaseUpdater:
         extension is loaded on GPU; None → the eager-autograd path runs."""
         from pdrl_amd import ops
 
+        # validated first, so a bad key also fails without the extension
+        wgrad_kernel = getattr(self.params, "wgrad_kernel", "sweep")
+        if wgrad_kernel not in ("sweep", "split"):
+            raise ValueError(
+                f"wgrad_kernel must be 'sweep' or 'split', got "
+                f"{wgrad_kernel!r}")
         if not (self.device.type == "cuda" and ops.available()):
             return None
         if not getattr(optimizer, "is_fused", False):
@@ -87,7 +93,8 @@ class BaseUpdater:
         use_graph = bool(int(os.environ.get("PDRL_USE_GRAPH", "1")))
         return FusedOnPolicyStep(algo, core, self.params, optimizer,
                                  grad_reducer=self.grad_reducer,
-                                 use_graph=use_graph, duals=duals)
+                                 use_graph=use_graph, duals=duals,
+                                 wgrad_kernel=wgrad_kernel)
 
     def apply_step(self, optimizer, parameters):
         """Gradient epilogue: all-reduce across ranks → clip → update.

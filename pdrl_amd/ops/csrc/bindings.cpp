@@ -1,6 +1,8 @@
 // Python bindings for the pdrl_amd CDNA4 HIP kernels.
 #include <torch/extension.h>
 
+#include <tuple>
+#include <utility>
 #include <vector>
 
 std::vector<at::Tensor> seq_lstm_forward_hip(
@@ -28,6 +30,15 @@ void seq_lstm_wgrad_out_hip(const at::Tensor&, const at::Tensor&,
                             const c10::optional<at::Tensor>&,
                             const c10::optional<at::Tensor>&, long, long,
                             double, double, double, double);
+void seq_lstm_wgrad_split_out_hip(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, at::Tensor&, at::Tensor&,
+    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+    const c10::optional<at::Tensor>&, at::Tensor&, at::Tensor&, long,
+    const c10::optional<at::Tensor>&, const c10::optional<at::Tensor>&, long,
+    long, double, double, double, double, const c10::optional<at::Tensor>&);
+std::tuple<long, long, long, long> seq_lstm_wgrad_split_plan(long, long, long,
+                                                             long, long);
 void seq_lstm_row_step_hip(
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
@@ -255,6 +266,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stats_part") = c10::nullopt, py::arg("stats") = c10::nullopt,
         py::arg("algo") = 0, py::arg("B") = 0, py::arg("cp") = 0.0,
         py::arg("cv") = 0.0, py::arg("ce") = 0.0, py::arg("creg") = 0.0);
+  m.def("seq_lstm_wgrad_split_out", &seq_lstm_wgrad_split_out_hip,
+        "split-K wgrad (slab x output group grid, ticketed ordered reduce) "
+        "into caller buffers; no row cap, single-body cores only",
+        py::arg("x"), py::arg("h0"), py::arg("stash"), py::arg("dgates"),
+        py::arg("dxb"), py::arg("gouts"), py::arg("dw_ih"), py::arg("dw_hh"),
+        py::arg("dbody_w"), py::arg("dbody_b"), py::arg("db_g"),
+        py::arg("dheads_w"), py::arg("dheads_b"), py::arg("norm_sq"),
+        // caller-owned and persistent; tickets zeroed once at allocation
+        py::arg("workspace"), py::arg("tickets"),
+        py::arg("slab_rows") = 0,  // 0: the host heuristic picks
+        py::arg("stats_part") = c10::nullopt, py::arg("stats") = c10::nullopt,
+        py::arg("algo") = 0, py::arg("B") = 0, py::arg("cp") = 0.0,
+        py::arg("cv") = 0.0, py::arg("ce") = 0.0, py::arg("creg") = 0.0,
+        py::arg("x2") = c10::nullopt);  // rejected: dual-body is out of scope
+  m.def(
+      "seq_lstm_wgrad_split_workspace",
+      [](long N, long H, long F, long D, long slab_rows) {
+        auto plan = seq_lstm_wgrad_split_plan(N, H, F, D, slab_rows);
+        return std::make_pair(std::get<0>(plan), std::get<1>(plan));
+      },
+      "(workspace floats, int32 tickets) seq_lstm_wgrad_split_out needs",
+      py::arg("N"), py::arg("H"), py::arg("F"), py::arg("D"),
+      py::arg("slab_rows") = 0);
+  m.def("seq_lstm_wgrad_split_plan", &seq_lstm_wgrad_split_plan,
+        "(workspace floats, tickets, slab rows, slabs) for one shape",
+        py::arg("N"), py::arg("H"), py::arg("F"), py::arg("D"),
+        py::arg("slab_rows") = 0);
   m.def("seq_lstm_forward_multi", &seq_lstm_forward_multi_hip,
         "multi-network fused forward (device pointer tables; dual-body "
         "rows carry body2/x2 pointers)",

@@ -15,6 +15,8 @@ default; profiles/row_step.md):
   2. seq_lstm_wgrad_out — MFMA weight-grad GEMMs written DIRECTLY into the
                           flat grad buffer's parameter views; one extra
                           block reduces the stat partials
+                          (wgrad_kernel="split": seq_lstm_wgrad_split_out,
+                          the split-K kernel without the 8192-row cap)
   3. rmsprop/adam       — fused clip + update
      [world > 1: RCCL all-reduce of the flat bucket before the update]
 
@@ -59,7 +61,8 @@ _VMPO_STATS = ["loss-total", "loss-policy", "loss-value", "eta", "alpha", "kl"]
 BATCH_FIELDS = ["obs", "act", "rew", "logits", "log_prob", "is_fir", "hx", "cx"]
 
 _ALGO_ID = {"IMPALA": 0, "PPO": 1, "PPO-C": 2, "V-MPO": 3}  # csrc/loss_row.h
-_WGRAD_MAX_ROWS = 8192          # row-pointer table of the wgrad kernels (LDS)
+_WGRAD_MAX_ROWS = 8192          # row-pointer table of the sweep wgrad (LDS)
+WGRAD_KERNELS = ("sweep", "split")
 _ROW_STEP_MAX_LDS_BYTES = 64 * 1024  # dynamic LDS of one launch
 _VMPO_MID_LDS_BYTES = 56 * 1024  # vmpo_mid keeps s_adv + s_psi (BT each) in LDS
 
@@ -133,8 +136,13 @@ class FusedOnPolicyStep(GraphableStep):
     _split_failed = False
 
     def __init__(self, algo: str, core, params, optimizer, grad_reducer=None,
-                 use_graph: bool = True, duals=None):
+                 use_graph: bool = True, duals=None,
+                 wgrad_kernel: str = "sweep"):
         assert algo in _ALGO_ID
+        if wgrad_kernel not in WGRAD_KERNELS:
+            raise ValueError(f"wgrad_kernel must be 'sweep' or 'split', got "
+                             f"{wgrad_kernel!r}")
+        self.wgrad_kernel = wgrad_kernel
         self.algo = algo
         self.core = core
         self.params = params
@@ -180,9 +188,9 @@ class FusedOnPolicyStep(GraphableStep):
     def fits(self, batch) -> bool:
         """Whether the fused step covers this shape; updaters fall back to
         eager autograd when it does not. The row-local losses have no shape
-        cap of their own."""
+        cap of their own, and neither has the split-K weight gradient."""
         B, S, _ = batch["obs"].shape
-        if B * S > _WGRAD_MAX_ROWS:
+        if self.wgrad_kernel == "sweep" and B * S > _WGRAD_MAX_ROWS:
             return False
         if self.algo == "V-MPO":
             return 2 * B * (S - 1) * 4 <= _VMPO_MID_LDS_BYTES
@@ -223,6 +231,15 @@ class FusedOnPolicyStep(GraphableStep):
                 "stash": mk(B, S, 7 * H),
                 "dgates": mk(B, S, 4 * H), "dxb": mk(B, S, H),
             })
+        if self.wgrad_kernel == "split":
+            # per-slab partial gradients and one ticket counter per output
+            # group; the kernel leaves the counters at 0, so they are zeroed
+            # here once and a graph replay needs no memset
+            floats, tickets = ext().seq_lstm_wgrad_split_workspace(
+                B * S, H, c.body_w.size(0), D)
+            ws["wg_ws"] = mk(max(floats, 1))
+            ws["wg_tickets"] = torch.zeros(tickets, dtype=torch.int32,
+                                           device=dev)
         self._ws, self._ws_shape = ws, (B, S)
         return ws
 
@@ -339,9 +356,15 @@ class FusedOnPolicyStep(GraphableStep):
         x = batch["obs"]
         ws = self._workspace(x.size(0), x.size(1))
         hx0, stash, dgates, dxb, stats_kw = self._loss(e, batch, ws)
-        e.seq_lstm_wgrad_out(x, hx0, stash, dgates, dxb, ws["gouts"],
-                             *self._grad_views(), self._norm_buf(),
-                             **stats_kw)
+        if self.wgrad_kernel == "split":
+            e.seq_lstm_wgrad_split_out(x, hx0, stash, dgates, dxb,
+                                       ws["gouts"], *self._grad_views(),
+                                       self._norm_buf(), ws["wg_ws"],
+                                       ws["wg_tickets"], 0, **stats_kw)
+        else:
+            e.seq_lstm_wgrad_out(x, hx0, stash, dgates, dxb, ws["gouts"],
+                                 *self._grad_views(), self._norm_buf(),
+                                 **stats_kw)
         if not update:
             return
         if self.grad_reducer is not None:

@@ -21,6 +21,7 @@ SRC = [
     "pdrl_amd/ops/csrc/bindings.cpp",
     "pdrl_amd/ops/csrc/seq_lstm.hip",
     "pdrl_amd/ops/csrc/wgrad.hip",
+    "pdrl_amd/ops/csrc/wgrad_split.hip",
     "pdrl_amd/ops/csrc/vmpo_loss.hip",
     "pdrl_amd/ops/csrc/sac_loss.hip",
     "pdrl_amd/ops/csrc/sacc_loss.hip",
