@@ -68,6 +68,11 @@ class BaseUpdater:
             raise ValueError(
                 f"wgrad_kernel must be 'sweep' or 'split', got "
                 f"{wgrad_kernel!r}")
+        vmpo_mid_kernel = getattr(self.params, "vmpo_mid_kernel", "block")
+        if vmpo_mid_kernel not in ("block", "wide"):
+            raise ValueError(
+                f"vmpo_mid_kernel must be 'block' or 'wide', got "
+                f"{vmpo_mid_kernel!r}")
         if not (self.device.type == "cuda" and ops.available()):
             return None
         if not getattr(optimizer, "is_fused", False):
@@ -94,7 +99,8 @@ class BaseUpdater:
         return FusedOnPolicyStep(algo, core, self.params, optimizer,
                                  grad_reducer=self.grad_reducer,
                                  use_graph=use_graph, duals=duals,
-                                 wgrad_kernel=wgrad_kernel)
+                                 wgrad_kernel=wgrad_kernel,
+                                 vmpo_mid_kernel=vmpo_mid_kernel)
 
     def apply_step(self, optimizer, parameters):
         """Gradient epilogue: all-reduce across ranks → clip → update.

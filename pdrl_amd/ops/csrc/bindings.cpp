@@ -128,6 +128,15 @@ bool vmpo_mid_hip(const at::Tensor&, const at::Tensor&, const at::Tensor&,
                   at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
                   const c10::optional<at::Tensor>&, at::Tensor&, long,
                   double, double, double, double, double, double);
+void vmpo_mid_wide_hip(const at::Tensor&, const at::Tensor&,
+                       const at::Tensor&, const at::Tensor&,
+                       const at::Tensor&, const at::Tensor&,
+                       const at::Tensor&, const at::Tensor&, at::Tensor&,
+                       at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+                       const c10::optional<at::Tensor>&, at::Tensor&, long,
+                       double, double, double, double, double, double,
+                       at::Tensor&, at::Tensor&, long);
+std::pair<long, long> vmpo_mid_wide_workspace(long, long);
 at::Tensor gae_hip(const at::Tensor&, double, double, const at::Tensor&);
 std::vector<at::Tensor> vtrace_hip(const at::Tensor&, const at::Tensor&,
                                    const at::Tensor&, const at::Tensor&,
@@ -433,6 +442,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gouts"), py::arg("cp"), py::arg("cv"), py::arg("creg"));
   m.def("vmpo_mid", &vmpo_mid_hip,
         "V-MPO cross-row middle kernel: selection + psi + duals + stats");
+  m.def("vmpo_mid_wide", &vmpo_mid_wide_hip,
+        "vmpo_mid over several workgroups (slab grid, redundant selection, "
+        "ticketed ordered reduce): same inputs and outputs, no B*(S-1) cap",
+        py::arg("mo"), py::arg("behav"), py::arg("logp"), py::arg("lse"),
+        py::arg("adv"), py::arg("td"), py::arg("log_eta"),
+        py::arg("log_alpha"), py::arg("psi"), py::arg("scalars"),
+        py::arg("g_eta"), py::arg("g_alpha"), py::arg("stats"),
+        py::arg("norm_sq"), py::arg("rng_state"), py::arg("A"), py::arg("cp"),
+        py::arg("cv"), py::arg("creg"), py::arg("eps_eta"),
+        py::arg("alpha_below"), py::arg("alpha_upper"),
+        // caller-owned and persistent; tickets zeroed once at allocation
+        py::arg("ws"), py::arg("tickets"),
+        py::arg("slab") = 0);  // 0: the host heuristic picks
+  m.def("vmpo_mid_wide_workspace", &vmpo_mid_wide_workspace,
+        "(workspace floats, int32 tickets) vmpo_mid_wide needs",
+        py::arg("BT"), py::arg("slab") = 0);
   m.def("gae", &gae_hip, "GAE reverse scan");
   m.def("vtrace", &vtrace_hip, "fused V-trace scan",
         pybind11::arg("behav_lp"), pybind11::arg("target_lp"),

@@ -25,6 +25,8 @@ more rows than CUs, where the row step measured slower):
   1. seq_lstm_fwd_loss  — forward + the log-softmax + GAE pre-phase
   2. vmpo_mid           — single-block cross-row kernel (radix-256 top-half
                           selection, psi softmax, eta/alpha duals, stats)
+                          (vmpo_mid_kernel="wide": vmpo_mid_wide, the same
+                          phase over several workgroups, no B·(S−1) cap)
   3. seq_lstm_bwd_fin   — the analytic grad emission + BPTT per row (for
                           the other algorithms: stat-partial reduce in
                           block 0 + BPTT; kept as the row step's reference)
@@ -63,6 +65,7 @@ BATCH_FIELDS = ["obs", "act", "rew", "logits", "log_prob", "is_fir", "hx", "cx"]
 _ALGO_ID = {"IMPALA": 0, "PPO": 1, "PPO-C": 2, "V-MPO": 3}  # csrc/loss_row.h
 _WGRAD_MAX_ROWS = 8192          # row-pointer table of the sweep wgrad (LDS)
 WGRAD_KERNELS = ("sweep", "split")
+VMPO_MID_KERNELS = ("block", "wide")
 _ROW_STEP_MAX_LDS_BYTES = 64 * 1024  # dynamic LDS of one launch
 _VMPO_MID_LDS_BYTES = 56 * 1024  # vmpo_mid keeps s_adv + s_psi (BT each) in LDS
 
@@ -137,12 +140,17 @@ class FusedOnPolicyStep(GraphableStep):
 
     def __init__(self, algo: str, core, params, optimizer, grad_reducer=None,
                  use_graph: bool = True, duals=None,
-                 wgrad_kernel: str = "sweep"):
+                 wgrad_kernel: str = "sweep",
+                 vmpo_mid_kernel: str = "block"):
         assert algo in _ALGO_ID
         if wgrad_kernel not in WGRAD_KERNELS:
             raise ValueError(f"wgrad_kernel must be 'sweep' or 'split', got "
                              f"{wgrad_kernel!r}")
+        if vmpo_mid_kernel not in VMPO_MID_KERNELS:
+            raise ValueError(f"vmpo_mid_kernel must be 'block' or 'wide', got "
+                             f"{vmpo_mid_kernel!r}")
         self.wgrad_kernel = wgrad_kernel
+        self.vmpo_mid_kernel = vmpo_mid_kernel
         self.algo = algo
         self.core = core
         self.params = params
@@ -188,11 +196,12 @@ class FusedOnPolicyStep(GraphableStep):
     def fits(self, batch) -> bool:
         """Whether the fused step covers this shape; updaters fall back to
         eager autograd when it does not. The row-local losses have no shape
-        cap of their own, and neither has the split-K weight gradient."""
+        cap of their own, and neither have the split-K weight gradient and
+        V-MPO's wide middle kernel."""
         B, S, _ = batch["obs"].shape
         if self.wgrad_kernel == "sweep" and B * S > _WGRAD_MAX_ROWS:
             return False
-        if self.algo == "V-MPO":
+        if self.algo == "V-MPO" and self.vmpo_mid_kernel == "block":
             return 2 * B * (S - 1) * 4 <= _VMPO_MID_LDS_BYTES
         return True
 
@@ -225,6 +234,13 @@ class FusedOnPolicyStep(GraphableStep):
                 "vm_adv": mk(BT), "vm_td": mk(BT), "vm_psi": mk(BT),
                 "vm_scalars": mk(8),
             })
+            if self.vmpo_mid_kernel == "wide":
+                # one slot of partial sums per slab and one ticket counter,
+                # zeroed here once: the kernel leaves it at 0
+                floats, tickets = ext().vmpo_mid_wide_workspace(BT)
+                ws["vm_ws"] = mk(max(floats, 1))
+                ws["vm_tickets"] = torch.zeros(tickets, dtype=torch.int32,
+                                               device=dev)
         if self.fused_rows:
             ws.update({
                 "outs": mk(B, S, D), "hS": mk(B, H), "cS": mk(B, H),
@@ -318,14 +334,16 @@ class FusedOnPolicyStep(GraphableStep):
         if vmpo:
             behav_logits = batch["logits"].reshape(B * S, self.A)
             log_eta, log_alpha = self.duals
-            if not e.vmpo_mid(
+            mid_args = (
                 outs, behav_logits, ws["vm_logp"], ws["vm_lse"],
                 ws["vm_adv"], ws["vm_td"], log_eta.data.view(1),
                 log_alpha.data.view(1), ws["vm_psi"], ws["vm_scalars"],
                 log_eta.grad.view(1), log_alpha.grad.view(1), self.stats_buf,
                 norm, self.rng_state, self.A, coefs[0], coefs[1], coefs[3],
-                p.coef_eta, p.coef_alpha_below, p.coef_alpha_upper,
-            ):
+                p.coef_eta, p.coef_alpha_below, p.coef_alpha_upper)
+            if self.vmpo_mid_kernel == "wide":
+                e.vmpo_mid_wide(*mid_args, ws["vm_ws"], ws["vm_tickets"], 0)
+            elif not e.vmpo_mid(*mid_args):
                 raise RuntimeError(
                     f"V-MPO batch ({B}, {S}) exceeds vmpo_mid's LDS; gate "
                     "on fits() and fall back to the eager step")
