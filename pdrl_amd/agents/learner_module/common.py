@@ -73,6 +73,14 @@ class BaseUpdater:
             raise ValueError(
                 f"vmpo_mid_kernel must be 'block' or 'wide', got "
                 f"{vmpo_mid_kernel!r}")
+        rows_kernel = getattr(self.params, "rows_kernel", "row")
+        if rows_kernel not in ("row", "tile"):
+            raise ValueError(
+                f"rows_kernel must be 'row' or 'tile', got {rows_kernel!r}")
+        if rows_kernel == "tile" and int(self.params.hidden_size) != 64:
+            raise ValueError(
+                "rows_kernel 'tile' is built for hidden_size 64, got "
+                f"{self.params.hidden_size}")
         if not (self.device.type == "cuda" and ops.available()):
             return None
         if not getattr(optimizer, "is_fused", False):
@@ -100,7 +108,8 @@ class BaseUpdater:
                                  grad_reducer=self.grad_reducer,
                                  use_graph=use_graph, duals=duals,
                                  wgrad_kernel=wgrad_kernel,
-                                 vmpo_mid_kernel=vmpo_mid_kernel)
+                                 vmpo_mid_kernel=vmpo_mid_kernel,
+                                 rows_kernel=rows_kernel)
 
     def apply_step(self, optimizer, parameters):
         """Gradient epilogue: all-reduce across ranks → clip → update.

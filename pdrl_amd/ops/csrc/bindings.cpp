@@ -49,6 +49,15 @@ void seq_lstm_row_step_hip(
     const c10::optional<at::Tensor>&, at::Tensor&, at::Tensor&, long, double,
     double, double, double, double, double, double, double, double, double,
     double);
+void seq_lstm_fwd_tile_hip(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&);
+void seq_lstm_bwd_tile_hip(const at::Tensor&, const at::Tensor&,
+                           const at::Tensor&, const at::Tensor&,
+                           const at::Tensor&, const at::Tensor&, at::Tensor&,
+                           at::Tensor&);
 long seq_lstm_row_step_lds_bytes(long, long, long);
 long seq_lstm_row_step_split_lds_bytes(long, long, long);
 bool seq_lstm_row_step_uses_split(long, long, long);
@@ -406,6 +415,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "whether seq_lstm_row_step launches that instantiation (its LDS "
         "fits a launch)",
         py::arg("S"), py::arg("D"), py::arg("algo"));
+  m.def("seq_lstm_fwd_tile", &seq_lstm_fwd_tile_hip,
+        "forward for 16 batch rows per workgroup on MFMA (H=64), any S >= 1; "
+        "same tensors as the row forward, all outputs caller-allocated",
+        py::arg("x"), py::arg("h0"), py::arg("c0"), py::arg("body_w"),
+        py::arg("body_b"), py::arg("w_ih"), py::arg("w_hh"), py::arg("b_g"),
+        py::arg("heads_w"), py::arg("heads_b"), py::arg("outs"),
+        py::arg("hS"), py::arg("cS"), py::arg("stash"));
+  m.def("seq_lstm_bwd_tile", &seq_lstm_bwd_tile_hip,
+        "BPTT for 16 batch rows per workgroup on MFMA (H=64): dgates and dxb "
+        "of leaf inputs, from the stash of either forward",
+        py::arg("gouts"), py::arg("stash"), py::arg("c0"), py::arg("w_ih"),
+        py::arg("w_hh"), py::arg("heads_w"), py::arg("dgates"),
+        py::arg("dxb"));
   m.def("seq_lstm_bwd_fin", &seq_lstm_bwd_fin_hip,
         "BPTT backward + stat finalization (or V-MPO grad emission)",
         py::arg("gouts"), py::arg("stash"), py::arg("x"), py::arg("c0"),

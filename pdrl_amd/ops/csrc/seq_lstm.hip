@@ -16,7 +16,10 @@
 // f32 VALU (guide §3: equal 157 TF rate) — so at this shape row-parallel
 // VALU with register-resident weights wins on occupancy, not on peak. The
 // framework's MFMA usage lives where the work IS GEMM-shaped with K≫16:
-// the weight-gradient kernels (wgrad.hip).
+// the weight-gradient kernels (wgrad.hip). The argument is about B = 128:
+// with thousands of rows a 16-row tile per workgroup fills the chip too and
+// fetches the weights 16× less often — seq_lstm_tile.hip, selected by
+// "rows_kernel": "tile" in the fused on-policy step.
 //
 // Weight residency:
 //   forward  — each thread owns one gate column: w_ih[:,g] and w_hh[:,g]

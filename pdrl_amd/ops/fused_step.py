@@ -38,6 +38,14 @@ functions behind their own thin launches —
   (V-MPO: vmpo_mid → vmpo_grad_rows) → seq_lstm_backward_core
 — then the weight-grad and optimizer launches as above.
 
+Row tiles (rows_kernel="tile", H=64, any algorithm; meant for B of 16 rows
+per CU and more, and the only recurrent kernels with no cap on S;
+profiles/rows_tile.md): the separate launches with the two recurrent ones
+swapped for csrc/seq_lstm_tile.hip, 16 batch rows per workgroup on MFMA —
+  seq_lstm_fwd_tile → onpolicy_loss_rows → onpolicy_stats_fin
+  (V-MPO: vmpo_mid | vmpo_mid_wide → vmpo_grad_rows) → seq_lstm_bwd_tile
+— on the workspace's buffers, then the weight-grad and optimizer launches.
+
 No host syncs anywhere; stats are read back only at the log interval.
 With hipGraph capture (`use_graph`), the whole step replays as one graph
 launch — single-rank; multi-rank splits into two graphs around the
@@ -66,6 +74,7 @@ _ALGO_ID = {"IMPALA": 0, "PPO": 1, "PPO-C": 2, "V-MPO": 3}  # csrc/loss_row.h
 _WGRAD_MAX_ROWS = 8192          # row-pointer table of the sweep wgrad (LDS)
 WGRAD_KERNELS = ("sweep", "split")
 VMPO_MID_KERNELS = ("block", "wide")
+ROWS_KERNELS = ("row", "tile")
 _ROW_STEP_MAX_LDS_BYTES = 64 * 1024  # dynamic LDS of one launch
 _VMPO_MID_LDS_BYTES = 56 * 1024  # vmpo_mid keeps s_adv + s_psi (BT each) in LDS
 
@@ -141,7 +150,8 @@ class FusedOnPolicyStep(GraphableStep):
     def __init__(self, algo: str, core, params, optimizer, grad_reducer=None,
                  use_graph: bool = True, duals=None,
                  wgrad_kernel: str = "sweep",
-                 vmpo_mid_kernel: str = "block"):
+                 vmpo_mid_kernel: str = "block",
+                 rows_kernel: str = "row"):
         assert algo in _ALGO_ID
         if wgrad_kernel not in WGRAD_KERNELS:
             raise ValueError(f"wgrad_kernel must be 'sweep' or 'split', got "
@@ -149,8 +159,15 @@ class FusedOnPolicyStep(GraphableStep):
         if vmpo_mid_kernel not in VMPO_MID_KERNELS:
             raise ValueError(f"vmpo_mid_kernel must be 'block' or 'wide', got "
                              f"{vmpo_mid_kernel!r}")
+        if rows_kernel not in ROWS_KERNELS:
+            raise ValueError(f"rows_kernel must be 'row' or 'tile', got "
+                             f"{rows_kernel!r}")
+        if rows_kernel == "tile" and core.w_ih.size(0) != 64:
+            raise ValueError("rows_kernel 'tile' is built for hidden size 64, "
+                             f"got {core.w_ih.size(0)}")
         self.wgrad_kernel = wgrad_kernel
         self.vmpo_mid_kernel = vmpo_mid_kernel
+        self.rows_kernel = rows_kernel
         self.algo = algo
         self.core = core
         self.params = params
@@ -170,6 +187,10 @@ class FusedOnPolicyStep(GraphableStep):
         # PDRL_FWDLOSS=0 selects the separate launches there too
         self.fused_rows = core.w_ih.size(0) == 64 and bool(
             int(os.environ.get("PDRL_FWDLOSS", "1")))
+        # the row tiles take the separate launches, on workspace buffers
+        self.tile_rows = rows_kernel == "tile"
+        if self.tile_rows:
+            self.fused_rows = False
         # forward + loss + BPTT in one launch wherever nothing crosses rows
         self.row_step = self.fused_rows and algo != "V-MPO"
         self.use_graph = use_graph
@@ -213,8 +234,9 @@ class FusedOnPolicyStep(GraphableStep):
     # ------------------------------------------------------------------ #
     def _workspace(self, B, S):
         """Persistent device scratch for one (B, S): head grads, per-row
-        loss partials, V-MPO's inter-phase buffers and — fused rows only,
-        the separate launches allocate their own — the activations."""
+        loss partials, V-MPO's inter-phase buffers and — fused rows and row
+        tiles; the other separate launches allocate their own — the
+        activations."""
         if self._ws_shape == (B, S):
             return self._ws
         c = self.core
@@ -241,7 +263,7 @@ class FusedOnPolicyStep(GraphableStep):
                 ws["vm_ws"] = mk(max(floats, 1))
                 ws["vm_tickets"] = torch.zeros(tickets, dtype=torch.int32,
                                                device=dev)
-        if self.fused_rows:
+        if self.fused_rows or self.tile_rows:
             ws.update({
                 "outs": mk(B, S, D), "hS": mk(B, H), "cS": mk(B, H),
                 "stash": mk(B, S, 7 * H),
@@ -326,6 +348,11 @@ class FusedOnPolicyStep(GraphableStep):
             outs, stash = ws["outs"], ws["stash"]
             e.seq_lstm_fwd_loss(x, hx0, cx0, *weights, outs, ws["hS"],
                                 ws["cS"], stash, *loss_args, **pre)
+        elif self.tile_rows:
+            outs, stash = ws["outs"], ws["stash"]
+            e.seq_lstm_fwd_tile(x, hx0, cx0, *weights, outs, ws["hS"],
+                                ws["cS"], stash)
+            e.onpolicy_loss_rows(outs, *loss_args, **pre)
         else:
             outs, _, _, stash = e.seq_lstm_forward(x, hx0, cx0, *weights)
             e.onpolicy_loss_rows(outs, *loss_args, **pre)
@@ -365,6 +392,11 @@ class FusedOnPolicyStep(GraphableStep):
             else:
                 e.onpolicy_stats_fin(part, self.stats_buf, algo_i, B, S, D,
                                      *coefs)
+            if self.tile_rows:
+                dgates, dxb = ws["dgates"], ws["dxb"]
+                e.seq_lstm_bwd_tile(gouts, stash, cx0, c.w_ih, c.w_hh,
+                                    c.heads_w, dgates, dxb)
+                return hx0, stash, dgates, dxb, {}
             _, _, _, dgates, dxb = e.seq_lstm_backward_core(
                 gouts, None, None, stash, x, cx0, *bwd_weights)
         return hx0, stash, dgates, dxb, {}

@@ -20,6 +20,7 @@ from torch.utils.cpp_extension import (  # noqa: E402
 SRC = [
     "pdrl_amd/ops/csrc/bindings.cpp",
     "pdrl_amd/ops/csrc/seq_lstm.hip",
+    "pdrl_amd/ops/csrc/seq_lstm_tile.hip",
     "pdrl_amd/ops/csrc/wgrad.hip",
     "pdrl_amd/ops/csrc/wgrad_split.hip",
     "pdrl_amd/ops/csrc/vmpo_loss.hip",
