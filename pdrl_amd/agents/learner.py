@@ -382,6 +382,9 @@ class Learner:
         it to the device replay and samples (``_make_replay``; one launch
         per update with ``"replay_kernel": "fused"``). The policy kind must match
         the env's action space. The ring is never read or written.
+        ``rollout_kernel`` picks the training rollout's geometry: ``"row"``,
+        one workgroup per env, or ``"tile"``, one per 16 envs on MFMA (hidden
+        size 64); greedy evaluation has the row geometry only.
         Env state is not checkpointed: a resumed run starts fresh episodes.
         """
         from pdrl_amd.ops.rollout import (DeviceRollout, has_device_env,
@@ -421,7 +424,8 @@ class Learner:
                 ou_sigma=float(getattr(p, "explore_ou_sigma", 0.6)))
         self.device_rollout = DeviceRollout(
             actor.core, p.env, n_envs, p.seq_len, self.device,
-            seed=1234 + self.rank, time_horizon=p.time_horizon, **explore)
+            seed=1234 + self.rank, time_horizon=p.time_horizon,
+            kernel=getattr(p, "rollout_kernel", "row"), **explore)
         self.is_root = self.rank == 0
         self.device_replay = None
         if not self.on_policy:

@@ -1,6 +1,6 @@
 // Device actor: fused policy-act + env-step kernels for CDNA4 (gfx950).
 //
-// Two kernels, each composed from a policy scheme and shared helpers:
+// Three kernels, each composed from a policy scheme and shared helpers:
 //
 //   rollout_train<H, Policy>  one launch advances N native environments by S
 //     steps and writes the (N, S, ·) batch in the learner's own field layout
@@ -8,6 +8,9 @@
 //     policy forward, sample, log-prob, env dynamics, termination and
 //     auto-reset never leave the GPU. Per-env state is carried from launch to
 //     launch. Bindings rollout_discrete and rollout_gaussian.
+//   rollout_train_tile<Policy>  the same contract at H = 64 with one workgroup
+//     per tile of 16 envs and the gates on MFMA (see there). Bindings
+//     rollout_discrete_tile and rollout_gaussian_tile.
 //   rollout_eval<H, Policy>   greedy evaluation: E whole episodes per env
 //     under the deterministic action, one return and one length per (env,
 //     episode), no batch, nothing persistent. Bindings rollout_eval_discrete
@@ -1236,6 +1239,343 @@ __global__ __launch_bounds__(4 * H) void rollout_eval(EvalArgs p) {
   }
 }
 
+// ---- row-tile training rollout ("rollout_kernel": "tile") -------------------
+// rollout_train gives one workgroup to one env: every workgroup pulls all of
+// w_ih and w_hh (128 KiB at H = 64) into registers for S steps of ONE env and
+// runs the gate GEMV on the VALU. Here one workgroup of 4 waves owns a tile of
+// 16 envs (H = 64, fp32) and reads and writes exactly the tensors of
+// rollout_train, with the env traits and the sampling schemes above as they
+// are; what changes is who calls them, and with which env's slice of LDS.
+//
+// Recurrent GEMM: gates(16×256) = [xb_t | h_{t-1}](16×128) · [w_ih ; w_hh] on
+// v_mfma_f32_16x16x4_f32 with the wave split, the K permutation and the row
+// stride of seq_lstm_fwd_tile_kernel (seq_lstm_tile.hip): wave w owns hidden
+// units 16w .. 16w+15 of all four gates, its 128 B fragments are loaded once
+// per launch, a lane (i = lane & 15, kq = lane >> 4) holds i, f, g, o of the
+// four (env 4kq + r, unit 16w + i) pairs, and c and the h that ``hx`` records
+// never leave its registers. The A tile [xb | h] is in LDS with a row stride
+// of 132 floats, double buffered by step parity: step t multiplies buffer
+// t & 1 and writes h_t into the other one, so no wave overwrites an h that
+// another is still multiplying.
+//
+// A step is a strict serial chain (the action of step t decides the
+// observation of step t + 1, so nothing is prefetched), four barriers:
+//   body      every thread: records the pre-step obs / hx / cx / is_fir, body
+//             GEMV + ReLU of the tile's 16 observations          — barrier 1
+//   gates     128 MFMAs per wave, activations, cell update, h_t → LDS
+//                                                                — barrier 2
+//   heads     wave 0: four lanes per env (lane = 16·part + env), K outputs
+//             of 16 terms each, summed part 0+1, 2+3, then both; lanes 0..15
+//             then hold their env's heads and run Policy::pre
+//   side      waves 1..3 meanwhile: Policy::side, side lane ("role") by side
+//             lane, 16 envs at a time in 16 adjacent lanes. Role r runs in
+//             wave 1 + r % 3, so the three heaviest roles (the candidate
+//             steps of a discrete env; normal, drift, first reset draw of a
+//             Gaussian one) take a wave each                     — barrier 3
+//   outcome   lanes 0..15 of wave 0, one env each: Policy::post, episode
+//             bookkeeping, Env::reset, next_obs; steps, run, the scheme's
+//             registers and the tick live in that lane over the S steps
+//                                                                — barrier 4
+//   reset     a reset flag per env in LDS: the lanes that own a reset env's
+//             (env, unit) pairs zero their c and h registers and their
+//             elements of the h row the next step multiplies.
+// Ragged tiles: envs ≥ N are clamped before any pointer arithmetic, their
+// loaded values are replaced by zeros, they skip pre / post (which store) and
+// store nothing; their lanes still reach every barrier.
+
+//
+// Every non-MFMA sum is one explicit fmaf chain in a stated order. The kernel
+// is NOT built with "no-packed-fp32-ops" as seq_lstm_tile.hip is: a kernel
+// whose target features differ from those of the env traits cannot inline
+// their plain (not force-inlined) step / reset / observe, and the calls cost
+// 48 B of scratch per lane. A packed form, where the compiler picks one,
+// rounds each of its two fmafs as the scalar form does and reorders no chain.
+
+using rt_f32x4 = __attribute__((ext_vector_type(4))) float;
+
+constexpr int kRtEnvs = 16;           // envs per workgroup
+constexpr int kRtH = 64;              // hidden size
+constexpr int kRtThreads = 256;       // 4 waves
+constexpr int kRtLd = 2 * kRtH + 4;   // LDS row stride of [xb | h], floats
+
+template <typename Policy>
+__global__ __launch_bounds__(kRtThreads) void rollout_train_tile(
+    typename Policy::Args p) {
+  using Env = typename Policy::Env;
+  constexpr int H = kRtH, G = 4 * kRtH, LD = kRtLd, T = kRtEnvs;
+  constexpr int F = Env::kObsDim;
+  constexpr int SD = EnvObs<Env>::kStateDim;
+  constexpr bool kIdentity = EnvObs<Env>::kIdentity;
+  static_assert(!kIdentity || SD == F, "identity env: the obs is the state");
+  constexpr int FE = kEnvLdsFloats<Env>;
+  constexpr int K = Policy::kHeads;
+  constexpr int R = Env::kResetDraws;
+  static_assert(R >= 1 && R <= 4, "reset draws use hash lanes 1..4");
+  static_assert(T * F <= kRtThreads && T * SD <= kRtThreads,
+                "one thread per observation / state value of the tile");
+
+  __shared__ __attribute__((aligned(16))) float a_s[2 * T * LD];  // xb | h
+  __shared__ __attribute__((aligned(16))) float hw_s[K * H];      // [a][k]
+  __shared__ float bw_s[F * H];
+  __shared__ float bb_s[H];
+  __shared__ float s_obs[T * FE];  // per env: obs (and state, if not the obs)
+  __shared__ float s_ur[T * R];    // per env: reset uniforms of the step
+  __shared__ typename Policy::Lds sp[T];
+  __shared__ float s_fir[T];
+  __shared__ int s_reset[T];
+
+  const int tid = threadIdx.x;
+  const int w = tid / kWave, lane = tid % kWave;
+  const int i = lane & 15, kq = lane >> 4;
+  const int u = 16 * w + i;  // this lane's hidden unit (accumulator column)
+  const int n0 = blockIdx.x * T;
+  const int S = p.S;
+
+  // B fragments: bf[g][4q+m] = [w_ih ; w_hh][16q + 4kq + m][g·H + u].
+  float bf[4][32];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const float* src = (q < 4) ? p.w_ih : p.w_hh;  // K = 64 .. 127 is w_hh
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+        bf[g][4 * q + m] = src[(16 * (q & 3) + 4 * kq + m) * G + g * H + u];
+    }
+  }
+  float bias[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) bias[g] = p.b_g[g * H + u];
+  float hb[K];
+#pragma unroll
+  for (int a = 0; a < K; ++a) hb[a] = p.heads_b[a];
+
+  for (int e = tid; e < F * H; e += kRtThreads) bw_s[e] = p.body_w[e];
+  for (int e = tid; e < K * H; e += kRtThreads)
+    hw_s[e] = p.heads_w[(e % H) * p.D + e / H];
+  if (tid < H) bb_s[tid] = p.body_b[tid];
+
+  // carried h / c of this lane's four (env, unit) pairs; h also into buffer 0
+  float c[4], h_last[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int n = n0 + 4 * kq + r;
+    const long nc = min(n, p.N - 1);
+    const float hv = p.h[nc * H + u], cv = p.c[nc * H + u];
+    h_last[r] = n < p.N ? hv : 0.0f;
+    c[r] = n < p.N ? cv : 0.0f;
+    a_s[(4 * kq + r) * LD + H + u] = h_last[r];
+  }
+
+  // Every thread serves env n0 + i in the scalar phases: lanes 0..15 of wave
+  // 0 own it, side lanes draw for it, so every thread tracks its tick.
+  const int n = n0 + i;
+  const bool live = n < p.N;
+  const int nc = min(n, p.N - 1);
+  const bool owner = tid < T;
+  float* const s_obs_e = s_obs + i * FE;
+  float* const s_state_e = env_state_lds<Env>(s_obs_e);
+  unsigned tick = p.tick[nc];
+  // side role of this thread (waves 1..3): role r runs in wave 1 + r % 3
+  const int role = 3 * kq + (w - 1);
+
+  if constexpr (kIdentity) {
+    if (tid < T * F) {
+      const int e = tid / F, k = tid % F;
+      const float v = p.env_state[(long)min(n0 + e, p.N - 1) * F + k];
+      s_obs[e * FE + k] = n0 + e < p.N ? v : 0.0f;
+    }
+  } else if (owner) {
+    float st[SD];
+#pragma unroll
+    for (int k = 0; k < SD; ++k) {
+      const float v = p.env_state[(long)nc * SD + k];
+      st[k] = live ? v : 0.0f;
+    }
+    publish_state<Env>(st, s_obs_e, s_state_e);
+  }
+  int steps = 0;
+  float run = 0.0f;
+  typename Policy::Regs regs;
+  if (owner) {
+    const float fir = p.is_fir[nc];
+    s_fir[tid] = live ? fir : 0.0f;
+    s_reset[tid] = 0;
+    steps = p.ep_steps[nc];
+    run = p.ep_run[nc];
+    regs.load(p, nc);
+  }
+#pragma unroll
+  for (int g = 0; g < 4; ++g) PDRL_PIN_REGS(bf[g], 32);
+  __syncthreads();
+
+  // thread (column tid % 64) covers envs 4·(tid / 64) .. +3 of the body
+  const int bk = tid % H, br0 = (tid / H) * 4;
+
+  for (int t = 0; t < S; ++t) {
+    float* a_cur = a_s + (t & 1) * T * LD;
+    float* a_nxt = a_s + ((t + 1) & 1) * T * LD;
+    const long row = (long)nc * S + t;  // a live env's row of the batch
+    tick += 1u;
+
+    // record the pre-step obs / is_fir / hx / cx
+    if (tid < T * F) {
+      const int e = tid / F, k = tid % F;
+      if (n0 + e < p.N)
+        p.obs[((long)(n0 + e) * S + t) * F + k] = s_obs[e * FE + k];
+    }
+    if (owner && live) p.is_fir_out[row] = s_fir[tid];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int nr = n0 + 4 * kq + r;
+      if (nr < p.N) {
+        p.hx[((long)nr * S + t) * H + u] = h_last[r];
+        p.cx[((long)nr * S + t) * H + u] = c[r];
+      }
+    }
+    // body: bias first, then k ascending (the row kernel's order)
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const int e = br0 + rr;
+      float acc = bb_s[bk];
+#pragma unroll
+      for (int k = 0; k < F; ++k)
+        acc = fmaf(s_obs[e * FE + k], bw_s[k * H + bk], acc);
+      a_cur[e * LD + bk] = fmaxf(acc, 0.0f);
+    }
+    __syncthreads();  // 1: xb_t (and the h row zeroed by a reset) visible
+
+    rt_f32x4 acc[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+      acc[g] = rt_f32x4{bias[g], bias[g], bias[g], bias[g]};
+    const rt_f32x4* ap =
+        reinterpret_cast<const rt_f32x4*>(a_cur + i * LD + 4 * kq);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const rt_f32x4 av = ap[4 * q];
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], bf[g][4 * q + m],
+                                                        acc[g], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float ig = sigmoidf_dev(acc[0][r]);
+      const float fg = sigmoidf_dev(acc[1][r]);
+      const float gg = tanhf(acc[2][r]);
+      const float og = sigmoidf_dev(acc[3][r]);
+      const float c_new = fg * c[r] + ig * gg;
+      const float h_new = og * tanhf(c_new);
+      c[r] = c_new;
+      h_last[r] = h_new;
+      a_nxt[(4 * kq + r) * LD + H + u] = h_new;
+    }
+    __syncthreads();  // 2: h_t visible
+
+    typename Policy::Choice ch;
+    if (w == 0) {
+      // heads of env i, terms 16kq .. 16kq+15 ascending in this lane
+      const rt_f32x4* hp =
+          reinterpret_cast<const rt_f32x4*>(a_nxt + i * LD + H + 16 * kq);
+      rt_f32x4 hv[4];
+#pragma unroll
+      for (int k4 = 0; k4 < 4; ++k4) hv[k4] = hp[k4];
+      float lg[K];
+#pragma unroll
+      for (int a = 0; a < K; ++a) {
+        const rt_f32x4* wp =
+            reinterpret_cast<const rt_f32x4*>(hw_s + a * H + 16 * kq);
+        float s = 0.0f;
+#pragma unroll
+        for (int k4 = 0; k4 < 4; ++k4) {
+          const rt_f32x4 wv = wp[k4];
+#pragma unroll
+          for (int m = 0; m < 4; ++m) s = fmaf(hv[k4][m], wv[m], s);
+        }
+        s += __shfl_xor(s, 16, kWave);
+        s += __shfl_xor(s, 32, kWave);
+        lg[a] = s + hb[a];
+      }
+      // lanes 0..15 hold their env's heads: no barrier needed
+      if (owner && live) Policy::pre(p, row, n, tick, lg, ch);
+    } else {
+      Policy::side(role, s_state_e, sp[i], s_ur + i * R, p.seed, n, tick);
+    }
+    __syncthreads();  // 3: the side results visible
+
+    // the step's outcome; termination, auto-reset (one lane per env)
+    if (owner && live) {
+      float st[SD];
+      float reward;
+      bool terminated;
+      Policy::post(p, row, n, tick, ch, regs, sp[tid], s_state_e, st, reward,
+                   terminated);
+      steps += 1;
+      run += reward;
+      p.rew[row] = reward;
+      const bool done = terminated || steps >= p.max_episode_steps;
+      const bool reset = done || steps >= p.time_horizon;
+      p.ep_ret[row] = reset ? run : kNoEpisode;
+      if (reset) {
+        Env::reset(st, s_ur + tid * R);
+        steps = 0;
+        run = 0.0f;
+        regs.reset();
+      }
+#pragma unroll
+      for (int k = 0; k < SD; ++k) s_state_e[k] = st[k];
+      if constexpr (!kIdentity) {
+        float ob[F];
+        Policy::next_obs(ch, sp[tid], reset, st, ob);
+#pragma unroll
+        for (int k = 0; k < F; ++k) s_obs_e[k] = ob[k];
+      }
+      s_fir[tid] = reset ? 1.0f : 0.0f;
+      s_reset[tid] = reset ? 1 : 0;
+    }
+    __syncthreads();  // 4: next observation and reset flags visible
+
+    // fresh recurrent state for the envs that reset: their c and h registers
+    // and their elements of the h row step t + 1 multiplies (written by this
+    // lane above, read behind barrier 1)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (s_reset[4 * kq + r] != 0) {
+        c[r] = 0.0f;
+        h_last[r] = 0.0f;
+        a_nxt[(4 * kq + r) * LD + H + u] = 0.0f;
+      }
+    }
+  }
+
+  // persist the per-env state for the next launch
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int nr = n0 + 4 * kq + r;
+    if (nr < p.N) {
+      p.h[(long)nr * H + u] = h_last[r];
+      p.c[(long)nr * H + u] = c[r];
+    }
+  }
+  if (tid < T * SD) {
+    const int e = tid / SD, k = tid % SD;
+    if (n0 + e < p.N)
+      p.env_state[(long)(n0 + e) * SD + k] =
+          env_state_lds<Env>(s_obs + e * FE)[k];
+  }
+  if (owner && live) {
+    p.is_fir[n] = s_fir[tid];
+    p.ep_steps[n] = steps;
+    p.ep_run[n] = run;
+    p.tick[n] = tick;
+    regs.store(p, n);
+  }
+}
+
 // ---- host side --------------------------------------------------------------
 // f(std::integral_constant<int, H>) launches one kernel for the hidden size.
 template <typename Fn>
@@ -1257,6 +1597,17 @@ void launch_train(const typename Policy::Args& a, int H) {
     hipLaunchKernelGGL((rollout_train<kH, Policy>), dim3(a.N), dim3(4 * kH),
                        0, current_stream(), a);
   });
+}
+
+// One workgroup per 16 envs (rollout_train_tile); H = 64 only.
+template <typename Policy>
+void launch_train_tile(const typename Policy::Args& a, int H) {
+  TORCH_CHECK(H == kRtH, "rollout tile kernels are built for hidden size ",
+              kRtH, ", got hidden size ", H);
+  hipLaunchKernelGGL((rollout_train_tile<Policy>),
+                     dim3((a.N + kRtEnvs - 1) / kRtEnvs), dim3(kRtThreads), 0,
+                     current_stream(), a);
+  HIP_CHECK_LAST();
 }
 
 template <typename Policy>
@@ -1441,8 +1792,9 @@ EvalArgs pack_eval_args(
 
 }  // namespace
 
-// Categorical policy. env_id: see with_discrete_env.
-void rollout_discrete_hip(
+// Categorical policy. env_id: see with_discrete_env. ``tile``: the row-tile
+// kernel (rollout_train_tile) instead of one workgroup per env.
+static void rollout_discrete_impl(
     const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
     const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
     const at::Tensor& heads_b, at::Tensor& env_state, at::Tensor& h,
@@ -1451,7 +1803,7 @@ void rollout_discrete_hip(
     at::Tensor& rew, at::Tensor& logits, at::Tensor& log_prob,
     at::Tensor& is_fir_out, at::Tensor& hx, at::Tensor& cx,
     at::Tensor& ep_ret, long env_id, long seed, long time_horizon,
-    long max_episode_steps) {
+    long max_episode_steps, bool tile) {
   with_discrete_env(env_id, [&](auto env, const char* env_msg) {
     using Policy = CategoricalSample<decltype(env)>;
     const RolloutArgs a = pack_rollout_args(
@@ -1460,14 +1812,42 @@ void rollout_discrete_hip(
         is_fir_out, hx, cx, ep_ret, Policy::Env::kObsDim, env_msg,
         EnvObs<typename Policy::Env>::kStateDim, Policy::kHeads, seed,
         time_horizon, max_episode_steps);
-    launch_train<Policy>(a, (int)body_w.size(1));
+    if (tile)
+      launch_train_tile<Policy>(a, (int)body_w.size(1));
+    else
+      launch_train<Policy>(a, (int)body_w.size(1));
   });
+}
+
+#define PDRL_ROLLOUT_DISCRETE_PARAMS                                          \
+  const at::Tensor &body_w, const at::Tensor &body_b, const at::Tensor &w_ih, \
+      const at::Tensor &w_hh, const at::Tensor &b_g,                          \
+      const at::Tensor &heads_w, const at::Tensor &heads_b,                   \
+      at::Tensor &env_state, at::Tensor &h, at::Tensor &c, at::Tensor &is_fir,\
+      at::Tensor &ep_steps, at::Tensor &ep_run, at::Tensor &tick,             \
+      at::Tensor &obs, at::Tensor &act, at::Tensor &rew, at::Tensor &logits,  \
+      at::Tensor &log_prob, at::Tensor &is_fir_out, at::Tensor &hx,           \
+      at::Tensor &cx, at::Tensor &ep_ret, long env_id, long seed,             \
+      long time_horizon, long max_episode_steps
+#define PDRL_ROLLOUT_DISCRETE_ARGS                                            \
+  body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, env_state, h, c, is_fir, \
+      ep_steps, ep_run, tick, obs, act, rew, logits, log_prob, is_fir_out,    \
+      hx, cx, ep_ret, env_id, seed, time_horizon, max_episode_steps
+
+void rollout_discrete_hip(PDRL_ROLLOUT_DISCRETE_PARAMS) {
+  rollout_discrete_impl(PDRL_ROLLOUT_DISCRETE_ARGS, false);
+}
+
+// Same contract on the row-tile kernel; H = 64 only.
+void rollout_discrete_tile_hip(PDRL_ROLLOUT_DISCRETE_PARAMS) {
+  rollout_discrete_impl(PDRL_ROLLOUT_DISCRETE_ARGS, true);
 }
 
 // Gaussian-policy sibling. env_id: see with_continuous_env. mode: 0 = heads
 // (mu, std), PPO-C sampling; 1 = heads (mu, log_std), SAC-C sampling with
-// optional OU exploration (ou_envs, warmup_steps; see GaussianArgs).
-void rollout_gaussian_hip(
+// optional OU exploration (ou_envs, warmup_steps; see GaussianArgs). ``tile``
+// as in rollout_discrete_impl.
+static void rollout_gaussian_impl(
     const at::Tensor& body_w, const at::Tensor& body_b, const at::Tensor& w_ih,
     const at::Tensor& w_hh, const at::Tensor& b_g, const at::Tensor& heads_w,
     const at::Tensor& heads_b, at::Tensor& env_state, at::Tensor& h,
@@ -1477,7 +1857,7 @@ void rollout_gaussian_hip(
     at::Tensor& log_prob, at::Tensor& is_fir_out, at::Tensor& hx,
     at::Tensor& cx, at::Tensor& ep_ret, long env_id, long mode, long seed,
     long time_horizon, long max_episode_steps, long ou_envs,
-    long warmup_steps, double ou_theta, double ou_sigma) {
+    long warmup_steps, double ou_theta, double ou_sigma, bool tile) {
   with_continuous_env(env_id, [&](auto env, const char* env_msg) {
     using Env = decltype(env);
     TORCH_CHECK(mode == 0 || mode == 1, "rollout: mode must be 0 or 1");
@@ -1501,11 +1881,42 @@ void rollout_gaussian_hip(
     a.warmup_steps = (unsigned)std::min<long>(warmup_steps, UINT32_MAX);
     a.ou_theta = (float)ou_theta;
     a.ou_sigma = (float)ou_sigma;
-    if (mode == 0)
-      launch_train<GaussianSample<Env, 0>>(a, (int)body_w.size(1));
+    const int H = (int)body_w.size(1);
+    if (tile && mode == 0)
+      launch_train_tile<GaussianSample<Env, 0>>(a, H);
+    else if (tile)
+      launch_train_tile<GaussianSample<Env, 1>>(a, H);
+    else if (mode == 0)
+      launch_train<GaussianSample<Env, 0>>(a, H);
     else
-      launch_train<GaussianSample<Env, 1>>(a, (int)body_w.size(1));
+      launch_train<GaussianSample<Env, 1>>(a, H);
   });
+}
+
+#define PDRL_ROLLOUT_GAUSSIAN_PARAMS                                          \
+  const at::Tensor &body_w, const at::Tensor &body_b, const at::Tensor &w_ih, \
+      const at::Tensor &w_hh, const at::Tensor &b_g,                          \
+      const at::Tensor &heads_w, const at::Tensor &heads_b,                   \
+      at::Tensor &env_state, at::Tensor &h, at::Tensor &c, at::Tensor &is_fir,\
+      at::Tensor &ep_steps, at::Tensor &ep_run, at::Tensor &tick,             \
+      at::Tensor &ou_state, at::Tensor &obs, at::Tensor &act, at::Tensor &rew,\
+      at::Tensor &logits, at::Tensor &log_prob, at::Tensor &is_fir_out,       \
+      at::Tensor &hx, at::Tensor &cx, at::Tensor &ep_ret, long env_id,        \
+      long mode, long seed, long time_horizon, long max_episode_steps,        \
+      long ou_envs, long warmup_steps, double ou_theta, double ou_sigma
+#define PDRL_ROLLOUT_GAUSSIAN_ARGS                                            \
+  body_w, body_b, w_ih, w_hh, b_g, heads_w, heads_b, env_state, h, c, is_fir, \
+      ep_steps, ep_run, tick, ou_state, obs, act, rew, logits, log_prob,      \
+      is_fir_out, hx, cx, ep_ret, env_id, mode, seed, time_horizon,           \
+      max_episode_steps, ou_envs, warmup_steps, ou_theta, ou_sigma
+
+void rollout_gaussian_hip(PDRL_ROLLOUT_GAUSSIAN_PARAMS) {
+  rollout_gaussian_impl(PDRL_ROLLOUT_GAUSSIAN_ARGS, false);
+}
+
+// Same contract on the row-tile kernel; H = 64 only.
+void rollout_gaussian_tile_hip(PDRL_ROLLOUT_GAUSSIAN_PARAMS) {
+  rollout_gaussian_impl(PDRL_ROLLOUT_GAUSSIAN_ARGS, true);
 }
 
 // Greedy evaluation: E = ep_ret.size(1) whole episodes per env in one launch.

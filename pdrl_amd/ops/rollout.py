@@ -6,7 +6,10 @@ termination, auto-reset — and returns the ``(N, S, dim)`` batch in the
 learner's own field layout (``buffers.rollout_fields``). On a GPU this is ONE
 launch of a HIP kernel of csrc/rollout.hip reading the core's live weights by
 pointer — ``rollout_discrete`` (categorical policy) or ``rollout_gaussian``
-(continuous control), chosen by the env's dynamics class; on a CPU device, or
+(continuous control), chosen by the env's dynamics class, each in two
+geometries chosen by ``kernel``: ``"row"``, one workgroup per env, or
+``"tile"`` (``rollout_*_tile``, hidden size 64), one workgroup per 16 envs
+with the gates on MFMA, same tensors and same random stream; on a CPU device, or
 with ``PDRL_ROLLOUT_EAGER=1``, the same class runs the pure-torch fp32
 reference below, which is both the CPU fallback and the kernels' oracle.
 
@@ -345,6 +348,8 @@ DEVICE_ENVS = {"CartPole-v1": CartPoleDyn,
 # head names[:2] → sampling scheme of a Gaussian policy (as the worker chooses)
 GAUSSIAN_MODES = {("mu", "std"): 0, ("mu", "log_std"): 1}
 HALF_LOG_2PI = 0.9189385
+# training rollout kernels: one workgroup per env | per tile of 16 envs (H = 64)
+ROLLOUT_KERNELS = ("row", "tile")
 
 
 def is_continuous_env(env_name: str) -> bool:
@@ -373,7 +378,14 @@ class DeviceRollout:
                  device, seed: int, time_horizon: int,
                  max_episode_steps: int | None = None, *, ou_envs: int = 0,
                  warmup_steps: int = 0, ou_theta: float = 0.15,
-                 ou_sigma: float = 0.6):
+                 ou_sigma: float = 0.6, kernel: str = "row"):
+        if kernel not in ROLLOUT_KERNELS:
+            raise ValueError(
+                f"rollout kernel must be 'row' or 'tile', got {kernel!r}")
+        if kernel == "tile" and core.hidden != 64:
+            raise ValueError("rollout kernel 'tile' is built for hidden size "
+                             f"64, got {core.hidden}")
+        self.kernel = kernel
         if env_name not in DEVICE_ENVS:
             raise ValueError(
                 f"env {env_name!r} has no device dynamics "
@@ -504,7 +516,9 @@ class DeviceRollout:
                 self._rollout_eager(ep_ret)
         elif self.continuous:
             b = self.batch
-            self._ext.rollout_gaussian(
+            launch = (self._ext.rollout_gaussian_tile if self.kernel == "tile"
+                      else self._ext.rollout_gaussian)
+            launch(
                 *(w.detach() for w in self._weights()),
                 self.env_state, self.h, self.c, self.is_fir, self.ep_steps,
                 self.ep_run, self.tick, self.ou_state, b["obs"], b["act"],
@@ -514,7 +528,9 @@ class DeviceRollout:
                 min(self.warmup_steps, _M32), self.ou_theta, self.ou_sigma)
         else:
             b = self.batch
-            self._ext.rollout_discrete(
+            launch = (self._ext.rollout_discrete_tile if self.kernel == "tile"
+                      else self._ext.rollout_discrete)
+            launch(
                 *(w.detach() for w in self._weights()),
                 self.env_state, self.h, self.c, self.is_fir, self.ep_steps,
                 self.ep_run, self.tick, b["obs"], b["act"], b["rew"],
