@@ -81,6 +81,12 @@ class SACUpdater(BaseUpdater):
         """Whole-step fused HIP DAG for discrete SAC (ops/sac_step.py)."""
         from pdrl_amd import ops
 
+        # validated first, so a bad key also fails without the extension
+        wgrad_kernel = getattr(self.params, "wgrad_kernel", "sweep")
+        if wgrad_kernel not in ("sweep", "split"):
+            raise ValueError(
+                f"wgrad_kernel must be 'sweep' or 'split', got "
+                f"{wgrad_kernel!r}")
         if not (self.device.type == "cuda" and ops.available()):
             return None
         if not all(getattr(o, "is_fused", False) for o in
@@ -95,7 +101,8 @@ class SACUpdater(BaseUpdater):
         from pdrl_amd.ops.sac_step import FusedSacStep
 
         use_graph = bool(int(os.environ.get("PDRL_USE_GRAPH", "1")))
-        return FusedSacStep(self, use_graph=use_graph)
+        return FusedSacStep(self, use_graph=use_graph,
+                            wgrad_kernel=wgrad_kernel)
 
     @property
     def alpha(self):

@@ -62,6 +62,12 @@ class SACContinuousUpdater(BaseUpdater):
 
         from pdrl_amd import ops
 
+        # validated first, so a bad key also fails without the extension
+        wgrad_kernel = getattr(self.params, "wgrad_kernel", "sweep")
+        if wgrad_kernel not in ("sweep", "split"):
+            raise ValueError(
+                f"wgrad_kernel must be 'sweep' or 'split', got "
+                f"{wgrad_kernel!r}")
         if not (self.device.type == "cuda" and ops.available()):
             return None
         if not all(getattr(o, "is_fused", False) for o in
@@ -75,7 +81,8 @@ class SACContinuousUpdater(BaseUpdater):
         from pdrl_amd.ops.sacc_step import FusedSacContinuousStep
 
         use_graph = bool(int(os.environ.get("PDRL_USE_GRAPH", "1")))
-        return FusedSacContinuousStep(self, use_graph=use_graph)
+        return FusedSacContinuousStep(self, use_graph=use_graph,
+                                      wgrad_kernel=wgrad_kernel)
 
     def trainable_modules(self):
         return {"model": self.model, "target_critic": self.target_critic}

@@ -220,6 +220,22 @@ void sac_actor_wgrad_hip(const at::Tensor&, const at::Tensor&,
                          const c10::optional<at::Tensor>&,
                          const c10::optional<at::Tensor>&, double, double,
                          double);
+void sac_actor_wgrad_split_hip(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, at::Tensor&, at::Tensor&,
+    at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+    const c10::optional<at::Tensor>&, const at::Tensor&, const at::Tensor&,
+    at::Tensor&, at::Tensor&, const c10::optional<at::Tensor>&,
+    const c10::optional<at::Tensor>&, double, double, double, at::Tensor&,
+    at::Tensor&, long);
+void seq_lstm_wgrad_split_multi_hip(const at::Tensor&, const at::Tensor&,
+                                    const at::Tensor&, long, long, at::Tensor&,
+                                    at::Tensor&, long,
+                                    const c10::optional<at::Tensor>&, long,
+                                    long);
+std::tuple<long, long> seq_lstm_wgrad_split_multi_workspace(long, long, long,
+                                                            long, long, long,
+                                                            long);
 void sac_fwd2_critic_loss_hip(
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
     const at::Tensor&, const at::Tensor&, const at::Tensor&,
@@ -342,6 +358,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("h0"), py::arg("tab"), py::arg("C"),
         py::arg("D"), py::arg("x2") = c10::nullopt, py::arg("F2") = 0,
         py::arg("half") = 0);
+  m.def("seq_lstm_wgrad_split_multi", &seq_lstm_wgrad_split_multi_hip,
+        "split-K weight grads of several networks in one launch (the 14-wide "
+        "table of seq_lstm_wgrad_multi; dual-body cores with x2); no row cap",
+        py::arg("x"), py::arg("h0"), py::arg("tab"), py::arg("nets"),
+        py::arg("D"), py::arg("workspace"), py::arg("tickets"),
+        py::arg("slab_rows") = 0, py::arg("x2") = c10::nullopt,
+        py::arg("F2") = 0, py::arg("half") = 0);
+  m.def("seq_lstm_wgrad_split_multi_workspace",
+        &seq_lstm_wgrad_split_multi_workspace,
+        "(workspace floats, int32 tickets) seq_lstm_wgrad_split_multi and "
+        "sac_actor_wgrad_split (nets = 1, F2 = 0) need",
+        py::arg("N"), py::arg("H"), py::arg("F"), py::arg("F2"), py::arg("D"),
+        py::arg("nets"), py::arg("slab_rows") = 0);
   m.def("rollout_discrete", &rollout_discrete_hip,
         "device actor: N envs x S steps of policy-act + env-step in one "
         "launch, writing the learner's (N,S,.) batch fields in place",
@@ -548,6 +577,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stats4"), py::arg("alpha_norm") = c10::nullopt,
         py::arg("clock") = c10::nullopt, py::arg("target_entropy") = 0.0,
         py::arg("beta1") = 0.9, py::arg("beta2") = 0.999);
+  m.def("sac_actor_wgrad_split", &sac_actor_wgrad_split_hip,
+        "sac_actor_wgrad on the split-K kernel: the same tail block, no row "
+        "cap",
+        py::arg("x"), py::arg("h0"), py::arg("stash"), py::arg("dgates"),
+        py::arg("dxb"), py::arg("gouts"), py::arg("dw_ih"), py::arg("dw_hh"),
+        py::arg("dbody_w"), py::arg("dbody_b"), py::arg("db_g"),
+        py::arg("dheads_w"), py::arg("dheads_b"), py::arg("norm_sq"),
+        py::arg("stats_part"), py::arg("log_alpha"), py::arg("g_alpha"),
+        py::arg("stats4"), py::arg("alpha_norm"), py::arg("clock"),
+        py::arg("target_entropy"), py::arg("beta1"), py::arg("beta2"),
+        py::arg("workspace"), py::arg("tickets"), py::arg("slab_rows") = 0);
   m.def("sac_fwd2_critic_loss", &sac_fwd2_critic_loss_hip,
         "post-update actor forward + SAC critic loss in one launch "
         "(fwd+loss pattern; vl partials reduced by the critic Adam)");

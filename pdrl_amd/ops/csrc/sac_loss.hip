@@ -16,6 +16,7 @@
 //                     dq1/dq2 on the taken actions. Zeroes the critic norm.
 #include "common.h"
 #include "core_rows.h"
+#include "sac_tail.h"
 #include "wgrad_body.h"
 
 namespace {
@@ -268,39 +269,9 @@ __global__ __launch_bounds__(256) void sac_actor_wgrad_kernel(
     float* __restrict__ stats4, float* __restrict__ alpha_norm,
     float* __restrict__ clock, int B, float target_entropy, float beta1,
     float beta2) {
-  const int tid = threadIdx.x;
   if ((int)blockIdx.x == (int)gridDim.x - 1) {
-    __shared__ float r0[256], r1[256];
-    float l = 0.f, en = 0.f;
-    for (int b = tid; b < B; b += 256) {
-      l += stats_part[2 * b];
-      en += stats_part[2 * b + 1];
-    }
-    r0[tid] = l;
-    r1[tid] = en;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-      if (tid < off) { r0[tid] += r0[tid + off]; r1[tid] += r1[tid + off]; }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      const float inv = 1.0f / N;
-      const float alpha = __expf(*log_alpha);
-      const float ent_mean = r1[0] * inv;
-      const float da = ent_mean - target_entropy;  // dlog_alpha
-      g_alpha[0] = da;
-      stats4[0] = r0[0] * inv;            // loss-actor
-      stats4[1] = __logf(alpha) * da;     // loss-alpha (value)
-      stats4[2] = alpha;
-      stats4[3] = ent_mean;
-      if (alpha_norm != nullptr) *alpha_norm = da * da;
-    }
-    if (tid == 1 && clock != nullptr) {
-      const float t = clock[0] + 1.0f;
-      clock[0] = t;
-      clock[1] = 1.0f - __powf(beta1, t);
-      clock[2] = 1.0f - __powf(beta2, t);
-    }
+    sac_actor_tail(stats_part, log_alpha, g_alpha, stats4, alpha_norm, clock,
+                   B, N, target_entropy, beta1, beta2);
     return;
   }
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];

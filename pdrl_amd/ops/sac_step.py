@@ -31,19 +31,34 @@ following the EAGER reference ordering exactly
 The twin-critic outputs from step 1 are reused for the value loss — the
 reference recomputes them after the actor update, but the critic parameters
 are unchanged in between, so the values are identical.
+
+wgrad_kernel="split" (the parameter file's "wgrad_kernel") swaps the weight
+gradient launches of both DAGs for their split-K forms and nothing else:
+sac_actor_wgrad -> sac_actor_wgrad_split and seq_lstm_wgrad_multi ->
+seq_lstm_wgrad_split_multi (csrc/wgrad_split_multi.hip), and on the legacy
+path seq_lstm_wgrad_out -> seq_lstm_wgrad_split_out. The sweep kernels stage
+a B*S-entry row table in LDS, which is the only reason fits() stops at 8192
+rows; the split kernels size nothing by B*S, so with "split" there is no row
+cap. The 8192-row gate of SeqLSTMCore.forward (the autograd path) is not
+touched.
 """
 from __future__ import annotations
 
 import torch
 
 from . import ext
-from .fused_step import GraphableStep
+from .fused_step import WGRAD_KERNELS, GraphableStep
 
 _SAC_STATS = ["loss-actor", "loss-alpha", "alpha", "entropy", "loss-value"]
 
 
 class FusedSacStep(GraphableStep):
-    def __init__(self, updater, use_graph: bool = True):
+    def __init__(self, updater, use_graph: bool = True,
+                 wgrad_kernel: str = "sweep"):
+        if wgrad_kernel not in WGRAD_KERNELS:
+            raise ValueError(f"wgrad_kernel must be 'sweep' or 'split', got "
+                             f"{wgrad_kernel!r}")
+        self.wgrad_kernel = wgrad_kernel
         self.u = updater
         self.params = updater.params
         self.grad_reducer = updater.grad_reducer
@@ -79,8 +94,9 @@ class FusedSacStep(GraphableStep):
 
     def fits(self, batch) -> bool:
         B, S, _ = batch["obs"].shape
-        # wgrad kernels stage a (B*S)-entry row-pointer table in LDS
-        return B * S <= 8192
+        # the sweep wgrad kernels stage a (B*S)-entry row-pointer table in
+        # LDS; the split-K ones size nothing by B*S
+        return self.wgrad_kernel == "split" or B * S <= 8192
 
     # ------------------------------------------------------------------ #
     def _multi_setup(self, batch):
@@ -201,7 +217,36 @@ class FusedSacStep(GraphableStep):
                     g[6].data_ptr(), nrm, 0, 0]
 
         self.wg_tab = t64([grow("q1"), grow("q2")])
+        if self.wgrad_kernel == "split":
+            # per-slab partial gradients and ticket counters of the twin
+            # critics' launch and of the actor's; the kernels leave the
+            # counters at 0, so they are zeroed here once and a graph replay
+            # needs no memset
+            e = ext()
+            F = x.size(2)
+
+            def ws(floats, tickets):
+                return (mk(max(floats, 1)),
+                        torch.zeros(tickets, dtype=torch.int32, device=dev))
+
+            self._ws_c = ws(*e.seq_lstm_wgrad_split_multi_workspace(
+                B * S, H, F, 0, D, 2))
+            if self._fast8:
+                self._ws_a = ws(*e.seq_lstm_wgrad_split_multi_workspace(
+                    B * S, H, F, 0, D, 1))
+            else:
+                self._ws_a = ws(*e.seq_lstm_wgrad_split_workspace(
+                    B * S, H, F, D))
         self._mshape = (B, S)
+
+    def _critic_wgrad(self, x, hx0):
+        """Twin-critic weight gradients: one launch, either kernel."""
+        e = ext()
+        if self.wgrad_kernel == "split":
+            e.seq_lstm_wgrad_split_multi(x, hx0, self.wg_tab, 2, self._D,
+                                         *self._ws_c)
+        else:
+            e.seq_lstm_wgrad_multi(x, hx0, self.wg_tab, 2, self._D)
 
     def _bwd_wgrad(self, core, gouts, stash, x, hx0, cx0, norm):
         e = ext()
@@ -214,9 +259,14 @@ class FusedSacStep(GraphableStep):
               core.heads_b.grad]
         assert all(g is not None for g in gs)
         # kernel order: dw_ih, dw_hh, dbody_w, dbody_b, db_g, dheads_w, dheads_b
-        e.seq_lstm_wgrad_out(x, hx0, stash, dgates, dxb, gouts,
-                             gs[2], gs[3], gs[0], gs[1], gs[4], gs[5], gs[6],
-                             norm)
+        if self.wgrad_kernel == "split":
+            e.seq_lstm_wgrad_split_out(x, hx0, stash, dgates, dxb, gouts,
+                                       gs[2], gs[3], gs[0], gs[1], gs[4],
+                                       gs[5], gs[6], norm, *self._ws_a, 0)
+        else:
+            e.seq_lstm_wgrad_out(x, hx0, stash, dgates, dxb, gouts,
+                                 gs[2], gs[3], gs[0], gs[1], gs[4], gs[5],
+                                 gs[6], norm)
 
     def _opt(self, optimizer):
         """Apply a fused optimizer whose ||grad||² was accumulated by the
@@ -267,15 +317,17 @@ class FusedSacStep(GraphableStep):
         #    Adam clock prep — ONE launch (one extra block on the wgrad grid)
         gs = self._actor_grads
         clk = u.actor_optimizer if self.adam_aa is not None else None
-        e.sac_actor_wgrad(
+        split = self.wgrad_kernel == "split"
+        (e.sac_actor_wgrad_split if split else e.sac_actor_wgrad)(
             x, hx0, ab["stash"], ab["dgates"], ab["dxb"], ab["gA"],
             gs[2], gs[3], gs[0], gs[1], gs[4], gs[5], gs[6],
             u.actor_optimizer.norm_sq, self._sp_a, log_alpha,
-            u.log_alpha.grad.view(1), self.stats_buf[:4], alpha_norm=None,
-            clock=clk.state3 if clk is not None else None,
-            target_entropy=u.target_entropy,
-            beta1=clk.beta1 if clk is not None else 0.9,
-            beta2=clk.beta2 if clk is not None else 0.999,
+            u.log_alpha.grad.view(1), self.stats_buf[:4], None,
+            clk.state3 if clk is not None else None,
+            u.target_entropy,
+            clk.beta1 if clk is not None else 0.9,
+            clk.beta2 if clk is not None else 0.999,
+            *(self._ws_a if split else ()),
         )
         # 4. actor + alpha Adam — ONE multi-group launch
         if self.adam_aa is not None:
@@ -297,7 +349,7 @@ class FusedSacStep(GraphableStep):
         )
         # 6-7. twin-critic BPTT + MFMA wgrads — one launch each
         e.seq_lstm_backward_multi(x, cx0, self.bwd_in, self.bwd_out, 2, D)
-        e.seq_lstm_wgrad_multi(x, hx0, self.wg_tab, 2, D)
+        self._critic_wgrad(x, hx0)
         # 8. critic Adam + vl-stat reduce + Polyak target — ONE launch
         co = u.critic_optimizer
         e.adam_step(
@@ -377,7 +429,7 @@ class FusedSacStep(GraphableStep):
         )
         # 8. twin-critic backward + MFMA weight grads — one launch each
         e.seq_lstm_backward_multi(x, cx0, self.bwd_in, self.bwd_out, 2, D)
-        e.seq_lstm_wgrad_multi(x, hx0, self.wg_tab, 2, D)
+        self._critic_wgrad(x, hx0)
         self._opt(u.critic_optimizer)
 
         # 9. Polyak target update

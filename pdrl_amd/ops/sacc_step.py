@@ -33,19 +33,33 @@ sac_continuous/learning.py:13-151):
   10. twin-critic BPTT (one launch) + MFMA wgrads incl. encoder segments
       (one launch) → critic Adam
   11. Polyak soft_update (cached device pointer tables)
+
+wgrad_kernel="split" (the parameter file's "wgrad_kernel") swaps the weight
+gradient launches of both DAGs for their split-K forms and nothing else:
+sac_actor_wgrad -> sac_actor_wgrad_split and the dual-body
+seq_lstm_wgrad_multi -> seq_lstm_wgrad_split_multi
+(csrc/wgrad_split_multi.hip), and on the legacy path seq_lstm_wgrad_out ->
+seq_lstm_wgrad_split_out. With "split" fits() has no row cap (the sweep
+kernels' B*S-entry LDS row table is the only reason for the 8192 rows). The
+8192-row gate of SeqLSTMCore.forward (the autograd path) is not touched.
 """
 from __future__ import annotations
 
 import torch
 
 from . import ext
-from .fused_step import GraphableStep
+from .fused_step import WGRAD_KERNELS, GraphableStep
 
 _SACC_STATS = ["loss-actor", "loss-alpha", "alpha", "entropy", "loss-value"]
 
 
 class FusedSacContinuousStep(GraphableStep):
-    def __init__(self, updater, use_graph: bool = True):
+    def __init__(self, updater, use_graph: bool = True,
+                 wgrad_kernel: str = "sweep"):
+        if wgrad_kernel not in WGRAD_KERNELS:
+            raise ValueError(f"wgrad_kernel must be 'sweep' or 'split', got "
+                             f"{wgrad_kernel!r}")
+        self.wgrad_kernel = wgrad_kernel
         self.u = updater
         self.params = updater.params
         self.grad_reducer = updater.grad_reducer
@@ -83,8 +97,9 @@ class FusedSacContinuousStep(GraphableStep):
 
     def fits(self, batch) -> bool:
         B, S, _ = batch["obs"].shape
-        # wgrad kernels stage a (B*S)-entry row-pointer table in LDS
-        return B * S <= 8192
+        # the sweep wgrad kernels stage a (B*S)-entry row-pointer table in
+        # LDS; the split-K ones size nothing by B*S
+        return self.wgrad_kernel == "split" or B * S <= 8192
 
     # ------------------------------------------------------------------ #
     def _multi_setup(self, batch):
@@ -226,7 +241,38 @@ class FusedSacContinuousStep(GraphableStep):
 
         self.wgB_tab = t64([grow(q["q1"], buf["q1b"]),
                             grow(q["q2"], buf["q2b"])])
+        if self.wgrad_kernel == "split":
+            # per-slab partial gradients and ticket counters of the twin
+            # critics' launch and of the actor's; the kernels leave the
+            # counters at 0, so they are zeroed here once and a graph replay
+            # needs no memset
+            e = ext()
+            F, Da = x.size(2), ac.heads_w.size(1)
+
+            def ws(floats, tickets):
+                return (mk(max(floats, 1)),
+                        torch.zeros(tickets, dtype=torch.int32, device=dev))
+
+            self._ws_c = ws(*e.seq_lstm_wgrad_split_multi_workspace(
+                B * S, H, F, A, 1, 2))
+            if self._fast11:
+                self._ws_a = ws(*e.seq_lstm_wgrad_split_multi_workspace(
+                    B * S, H, F, 0, Da, 1))
+            else:
+                self._ws_a = ws(*e.seq_lstm_wgrad_split_workspace(
+                    B * S, H, F, Da))
         self._mshape = (B, S)
+
+    def _critic_wgrad(self, x, hx0):
+        """Twin-critic weight gradients (the encoder grads ride the same
+        launch): one launch, either kernel."""
+        e = ext()
+        kw = dict(x2=self.buf["actb"], F2=self._A, half=self._half)
+        if self.wgrad_kernel == "split":
+            e.seq_lstm_wgrad_split_multi(x, hx0, self.wgB_tab, 2, 1,
+                                         *self._ws_c, 0, **kw)
+        else:
+            e.seq_lstm_wgrad_multi(x, hx0, self.wgB_tab, 2, 1, **kw)
 
     def _actor_fwd(self, x, hx0, cx0):
         e = ext()
@@ -248,9 +294,14 @@ class FusedSacContinuousStep(GraphableStep):
               core.w_hh.grad, core.b_g.grad, core.heads_w.grad,
               core.heads_b.grad]
         assert all(g is not None for g in gs)
-        e.seq_lstm_wgrad_out(x, hx0, stash, dgates, dxb, gouts,
-                             gs[2], gs[3], gs[0], gs[1], gs[4], gs[5], gs[6],
-                             norm)
+        if self.wgrad_kernel == "split":
+            e.seq_lstm_wgrad_split_out(x, hx0, stash, dgates, dxb, gouts,
+                                       gs[2], gs[3], gs[0], gs[1], gs[4],
+                                       gs[5], gs[6], norm, *self._ws_a, 0)
+        else:
+            e.seq_lstm_wgrad_out(x, hx0, stash, dgates, dxb, gouts,
+                                 gs[2], gs[3], gs[0], gs[1], gs[4], gs[5],
+                                 gs[6], norm)
 
     def _opt(self, optimizer):
         if self.grad_reducer is not None:
@@ -316,15 +367,17 @@ class FusedSacContinuousStep(GraphableStep):
         #    discrete reduce block applies verbatim)
         gs = self._actor_grads
         clk = u.actor_optimizer if self.adam_aa is not None else None
-        e.sac_actor_wgrad(
+        split = self.wgrad_kernel == "split"
+        (e.sac_actor_wgrad_split if split else e.sac_actor_wgrad)(
             x, hx0, buf["stA"], buf["adg"], buf["adx"], buf["dmoA"],
             gs[2], gs[3], gs[0], gs[1], gs[4], gs[5], gs[6],
             u.actor_optimizer.norm_sq, self._sp_a, log_alpha,
-            u.log_alpha.grad.view(1), self.stats_buf[:4], alpha_norm=None,
-            clock=clk.state3 if clk is not None else None,
-            target_entropy=u.target_entropy,
-            beta1=clk.beta1 if clk is not None else 0.9,
-            beta2=clk.beta2 if clk is not None else 0.999,
+            u.log_alpha.grad.view(1), self.stats_buf[:4], None,
+            clk.state3 if clk is not None else None,
+            u.target_entropy,
+            clk.beta1 if clk is not None else 0.9,
+            clk.beta2 if clk is not None else 0.999,
+            *(self._ws_a if split else ()),
         )
         # 6. actor + alpha Adam — ONE multi-group launch
         if self.adam_aa is not None:
@@ -356,8 +409,7 @@ class FusedSacContinuousStep(GraphableStep):
             buf["q2b"]["dgates"], buf["q2b"]["dxb"],
             p.gamma, p.reward_scale)
         # 10. twin-critic MFMA wgrads (encoder grads ride the same launch)
-        e.seq_lstm_wgrad_multi(x, hx0, self.wgB_tab, 2, 1, x2=buf["actb"],
-                               F2=A, half=half)
+        self._critic_wgrad(x, hx0)
         # 11. critic Adam + vl-stat reduce + Polyak target — ONE launch
         co = u.critic_optimizer
         e.adam_step(
@@ -454,8 +506,7 @@ class FusedSacContinuousStep(GraphableStep):
         #     same launch as dual-body segments)
         e.seq_lstm_backward_multi(x, cx0, self.bwdB_in, self.bwdB_out, 2, 1,
                                   F2=A, half=half)
-        e.seq_lstm_wgrad_multi(x, hx0, self.wgB_tab, 2, 1, x2=buf["actb"],
-                               F2=A, half=half)
+        self._critic_wgrad(x, hx0)
         self._opt(u.critic_optimizer)
 
         # 11. Polyak target update
