@@ -87,6 +87,14 @@ class SACUpdater(BaseUpdater):
             raise ValueError(
                 f"wgrad_kernel must be 'sweep' or 'split', got "
                 f"{wgrad_kernel!r}")
+        rows_kernel = getattr(self.params, "rows_kernel", "row")
+        if rows_kernel not in ("row", "tile"):
+            raise ValueError(
+                f"rows_kernel must be 'row' or 'tile', got {rows_kernel!r}")
+        if rows_kernel == "tile" and int(self.params.hidden_size) != 64:
+            raise ValueError(
+                "rows_kernel 'tile' is built for hidden_size 64, got "
+                f"{self.params.hidden_size}")
         if not (self.device.type == "cuda" and ops.available()):
             return None
         if not all(getattr(o, "is_fused", False) for o in
@@ -102,7 +110,8 @@ class SACUpdater(BaseUpdater):
 
         use_graph = bool(int(os.environ.get("PDRL_USE_GRAPH", "1")))
         return FusedSacStep(self, use_graph=use_graph,
-                            wgrad_kernel=wgrad_kernel)
+                            wgrad_kernel=wgrad_kernel,
+                            rows_kernel=rows_kernel)
 
     @property
     def alpha(self):

@@ -58,6 +58,12 @@ void seq_lstm_bwd_tile_hip(const at::Tensor&, const at::Tensor&,
                            const at::Tensor&, const at::Tensor&,
                            const at::Tensor&, const at::Tensor&, at::Tensor&,
                            at::Tensor&);
+void seq_lstm_fwd_tile_multi_hip(const at::Tensor&, const at::Tensor&,
+                                 const at::Tensor&, const at::Tensor&,
+                                 const at::Tensor&, long, long, long, long);
+void seq_lstm_bwd_tile_multi_hip(const at::Tensor&, const at::Tensor&,
+                                 const at::Tensor&, const at::Tensor&, long,
+                                 long, long, long, bool);
 long seq_lstm_row_step_lds_bytes(long, long, long);
 long seq_lstm_row_step_split_lds_bytes(long, long, long);
 bool seq_lstm_row_step_uses_split(long, long, long);
@@ -494,6 +500,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gouts"), py::arg("stash"), py::arg("c0"), py::arg("w_ih"),
         py::arg("w_hh"), py::arg("heads_w"), py::arg("dgates"),
         py::arg("dxb"));
+  m.def("seq_lstm_fwd_tile_multi", &seq_lstm_fwd_tile_multi_hip,
+        "seq_lstm_forward_multi on row tiles: 16 batch rows per workgroup on "
+        "MFMA (H=64), any S >= 1, the same device pointer tables",
+        py::arg("x"), py::arg("h0"), py::arg("c0"), py::arg("core_tab"),
+        py::arg("out_tab"), py::arg("C"), py::arg("D"), py::arg("F2") = 0,
+        py::arg("half") = 0);
+  m.def("seq_lstm_bwd_tile_multi", &seq_lstm_bwd_tile_multi_hip,
+        "seq_lstm_backward_multi on row tiles (H=64): dgates/dxb [+ dx2] of "
+        "leaf inputs, the same device pointer tables",
+        py::arg("x"), py::arg("c0"), py::arg("in_tab"), py::arg("out_tab"),
+        py::arg("C"), py::arg("D"), py::arg("F2") = 0, py::arg("half") = 0,
+        py::arg("accum_dx2") = false);
   m.def("seq_lstm_bwd_fin", &seq_lstm_bwd_fin_hip,
         "BPTT backward + stat finalization (or V-MPO grad emission)",
         py::arg("gouts"), py::arg("stash"), py::arg("x"), py::arg("c0"),

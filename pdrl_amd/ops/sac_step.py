@@ -41,24 +41,45 @@ a B*S-entry row table in LDS, which is the only reason fits() stops at 8192
 rows; the split kernels size nothing by B*S, so with "split" there is no row
 cap. The 8192-row gate of SeqLSTMCore.forward (the autograd path) is not
 touched.
+
+rows_kernel="tile" (the parameter file's "rows_kernel"; H = 64, meant for
+B in the thousands: profiles/sac_tile.md) runs the legacy sequence, single-
+or multi-rank, with its recurrent launches on row tiles, 16 batch rows per
+workgroup on MFMA, and nothing else changed:
+  seq_lstm_forward_multi  -> seq_lstm_fwd_tile_multi   (step 1)
+  seq_lstm_backward_multi -> seq_lstm_bwd_tile_multi   (step 8)
+  seq_lstm_forward        -> seq_lstm_fwd_tile         (step 5)
+  seq_lstm_backward_core  -> seq_lstm_bwd_tile         (step 3)
+(csrc/seq_lstm_tile_multi.hip takes the pointer tables built here as they
+are; csrc/seq_lstm_tile.hip writes into buffers this step owns.) The
+8-launch DAG fuses loss phases into the row kernels and is not taken.
 """
 from __future__ import annotations
 
 import torch
 
 from . import ext
-from .fused_step import WGRAD_KERNELS, GraphableStep
+from .fused_step import ROWS_KERNELS, WGRAD_KERNELS, GraphableStep
 
 _SAC_STATS = ["loss-actor", "loss-alpha", "alpha", "entropy", "loss-value"]
 
 
 class FusedSacStep(GraphableStep):
     def __init__(self, updater, use_graph: bool = True,
-                 wgrad_kernel: str = "sweep"):
+                 wgrad_kernel: str = "sweep", rows_kernel: str = "row"):
         if wgrad_kernel not in WGRAD_KERNELS:
             raise ValueError(f"wgrad_kernel must be 'sweep' or 'split', got "
                              f"{wgrad_kernel!r}")
+        if rows_kernel not in ROWS_KERNELS:
+            raise ValueError(f"rows_kernel must be 'row' or 'tile', got "
+                             f"{rows_kernel!r}")
+        hidden = updater.actor.core.w_ih.size(0)
+        if rows_kernel == "tile" and hidden != 64:
+            raise ValueError("rows_kernel 'tile' is built for hidden size 64, "
+                             f"got {hidden}")
         self.wgrad_kernel = wgrad_kernel
+        self.rows_kernel = rows_kernel
+        self.tile_rows = rows_kernel == "tile"
         self.u = updater
         self.params = updater.params
         self.grad_reducer = updater.grad_reducer
@@ -82,6 +103,8 @@ class FusedSacStep(GraphableStep):
         self._fast8 = (self.grad_reducer is None
                        and self.cores["actor"].w_ih.size(0) == 64
                        and bool(int(os.environ.get("PDRL_SAC8", "1"))))
+        if self.tile_rows:  # the legacy sequence on row tiles
+            self._fast8 = False
         # actor+alpha Adam updates happen back-to-back at the same DAG
         # point → one multi-group launch (shared device step clock)
         self.adam_aa = None
@@ -160,6 +183,16 @@ class FusedSacStep(GraphableStep):
                   ag.heads_b.grad]
             assert all(g is not None for g in gs)
             self._actor_grads = gs
+        elif self.tile_rows:
+            # the single-network tile launches write into caller-owned
+            # buffers: the actor's head grads, its BPTT outputs and the
+            # post-update logits (the re-forward reuses the actor's
+            # stash/hS/cS, dead once its weight gradients are out)
+            a = buf["actor"]
+            a["gA"] = mk(B, S, D)
+            a["dgates"] = mk(B, S, 4 * H)
+            a["dxb"] = mk(B, S, H)
+            buf["mo2"] = mk(B, S, D)
         self.buf = buf
 
         def t64(rows):
@@ -250,10 +283,15 @@ class FusedSacStep(GraphableStep):
 
     def _bwd_wgrad(self, core, gouts, stash, x, hx0, cx0, norm):
         e = ext()
-        _, _, _, dgates, dxb = e.seq_lstm_backward_core(
-            gouts, None, None, stash, x, cx0, core.body_w, core.w_ih,
-            core.w_hh, core.heads_w,
-        )
+        if self.tile_rows:
+            dgates, dxb = self.buf["actor"]["dgates"], self.buf["actor"]["dxb"]
+            e.seq_lstm_bwd_tile(gouts, stash, cx0, core.w_ih, core.w_hh,
+                                core.heads_w, dgates, dxb)
+        else:
+            _, _, _, dgates, dxb = e.seq_lstm_backward_core(
+                gouts, None, None, stash, x, cx0, core.body_w, core.w_ih,
+                core.w_hh, core.heads_w,
+            )
         gs = [core.body_w.grad, core.body_b.grad, core.w_ih.grad,
               core.w_hh.grad, core.b_g.grad, core.heads_w.grad,
               core.heads_b.grad]
@@ -381,14 +419,15 @@ class FusedSacStep(GraphableStep):
         # 1. actor + twin critics + twin TARGET critics — ONE 5-network
         #    launch (the targets' params are constant until the Polyak
         #    update at step 9, so their forward commutes with steps 2-5)
-        e.seq_lstm_forward_multi(x, hx0, cx0, self.fwd1_cores,
-                                 self.fwd1_outs, 5, D)
+        tile = self.tile_rows
+        (e.seq_lstm_fwd_tile_multi if tile else e.seq_lstm_forward_multi)(
+            x, hx0, cx0, self.fwd1_cores, self.fwd1_outs, 5, D)
         moA1 = buf["actor"]["outs"]
         mq1, mq2 = buf["q1"]["outs"], buf["q2"]["outs"]
 
         # 2. actor + temperature losses (analytic grads); the shared Adam
         #    clock is prepped inside this kernel (one less launch)
-        gA = torch.empty_like(moA1)
+        gA = buf["actor"]["gA"] if tile else torch.empty_like(moA1)
         clk = u.actor_optimizer if self.adam_aa is not None else None
         e.sac_actor_loss(
             moA1, mq1, mq2, log_alpha, gA, u.log_alpha.grad.view(1),
@@ -413,10 +452,17 @@ class FusedSacStep(GraphableStep):
         # 5. post-update actor forward (single network; the targets were
         #    already evaluated in the 5-network launch)
         ac = self.cores["actor"]
-        moA2, _, _, _ = e.seq_lstm_forward(
-            x, hx0, cx0, ac.body_w, ac.body_b, ac.w_ih, ac.w_hh, ac.b_g,
-            ac.heads_w, ac.heads_b,
-        )
+        if tile:
+            ab, moA2 = buf["actor"], buf["mo2"]
+            e.seq_lstm_fwd_tile(
+                x, hx0, cx0, ac.body_w, ac.body_b, ac.w_ih, ac.w_hh, ac.b_g,
+                ac.heads_w, ac.heads_b, moA2, ab["hS"], ab["cS"], ab["stash"],
+            )
+        else:
+            moA2, _, _, _ = e.seq_lstm_forward(
+                x, hx0, cx0, ac.body_w, ac.body_b, ac.w_ih, ac.w_hh, ac.b_g,
+                ac.heads_w, ac.heads_b,
+            )
         mt1, mt2 = buf["t1"]["outs"], buf["t2"]["outs"]
 
         # 7. critic losses (head grads land in the persistent gq buffers
@@ -428,7 +474,8 @@ class FusedSacStep(GraphableStep):
             p.gamma, p.reward_scale,
         )
         # 8. twin-critic backward + MFMA weight grads — one launch each
-        e.seq_lstm_backward_multi(x, cx0, self.bwd_in, self.bwd_out, 2, D)
+        (e.seq_lstm_bwd_tile_multi if tile else e.seq_lstm_backward_multi)(
+            x, cx0, self.bwd_in, self.bwd_out, 2, D)
         self._critic_wgrad(x, hx0)
         self._opt(u.critic_optimizer)
 

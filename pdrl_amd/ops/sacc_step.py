@@ -42,24 +42,47 @@ seq_lstm_wgrad_multi -> seq_lstm_wgrad_split_multi
 seq_lstm_wgrad_split_out. With "split" fits() has no row cap (the sweep
 kernels' B*S-entry LDS row table is the only reason for the 8192 rows). The
 8192-row gate of SeqLSTMCore.forward (the autograd path) is not touched.
+
+rows_kernel="tile" (the parameter file's "rows_kernel"; H = 64, meant for
+B in the thousands: profiles/sac_tile.md) runs the legacy sequence, single-
+or multi-rank, with its recurrent launches on row tiles, 16 batch rows per
+workgroup on MFMA, and nothing else changed:
+  seq_lstm_forward_multi  -> seq_lstm_fwd_tile_multi   (steps 2 and 8,
+                             dual body: x2 per network from the table)
+  seq_lstm_backward_multi -> seq_lstm_bwd_tile_multi   (step 4, with dx2
+                             accumulated into dact, and step 10)
+  seq_lstm_forward        -> seq_lstm_fwd_tile         (steps 1 and 7)
+  seq_lstm_backward_core  -> seq_lstm_bwd_tile         (step 6)
+(csrc/seq_lstm_tile_multi.hip takes the pointer tables built here as they
+are; csrc/seq_lstm_tile.hip writes into buffers this step owns.) The
+11-launch DAG fuses loss phases into the row kernels and is not taken.
 """
 from __future__ import annotations
 
 import torch
 
 from . import ext
-from .fused_step import WGRAD_KERNELS, GraphableStep
+from .fused_step import ROWS_KERNELS, WGRAD_KERNELS, GraphableStep
 
 _SACC_STATS = ["loss-actor", "loss-alpha", "alpha", "entropy", "loss-value"]
 
 
 class FusedSacContinuousStep(GraphableStep):
     def __init__(self, updater, use_graph: bool = True,
-                 wgrad_kernel: str = "sweep"):
+                 wgrad_kernel: str = "sweep", rows_kernel: str = "row"):
         if wgrad_kernel not in WGRAD_KERNELS:
             raise ValueError(f"wgrad_kernel must be 'sweep' or 'split', got "
                              f"{wgrad_kernel!r}")
+        if rows_kernel not in ROWS_KERNELS:
+            raise ValueError(f"rows_kernel must be 'row' or 'tile', got "
+                             f"{rows_kernel!r}")
+        hidden = updater.actor.core.w_ih.size(0)
+        if rows_kernel == "tile" and hidden != 64:
+            raise ValueError("rows_kernel 'tile' is built for hidden size 64, "
+                             f"got {hidden}")
         self.wgrad_kernel = wgrad_kernel
+        self.rows_kernel = rows_kernel
+        self.tile_rows = rows_kernel == "tile"
         self.u = updater
         self.params = updater.params
         self.grad_reducer = updater.grad_reducer
@@ -85,6 +108,8 @@ class FusedSacContinuousStep(GraphableStep):
         self._fast11 = (self.grad_reducer is None
                         and self.actor_core.w_ih.size(0) == 64
                         and bool(int(os.environ.get("PDRL_SAC8", "1"))))
+        if self.tile_rows:  # the legacy sequence on row tiles
+            self._fast11 = False
         # actor+alpha Adam updates batch into one launch (shared clock)
         self.adam_aa = None
         if self.grad_reducer is None and getattr(
@@ -164,6 +189,19 @@ class FusedSacContinuousStep(GraphableStep):
                   ag.heads_b.grad]
             assert all(g is not None for g in gs)
             self._actor_grads = gs
+        elif self.tile_rows:
+            # the single-network tile launches write into caller-owned
+            # buffers: both actor forwards (the second reuses the first's
+            # stash/hS/cS, dead once the actor's weight gradients are out),
+            # the actor's head grads and its BPTT outputs
+            buf["moA"] = mk(B, S, 2 * A)
+            buf["moA2"] = mk(B, S, 2 * A)
+            buf["dmoA"] = mk(B, S, 2 * A)
+            buf["stA"] = mk(B, S, 7 * H)
+            buf["hA"] = mk(B, H)
+            buf["cA"] = mk(B, H)
+            buf["adg"] = mk(B, S, 4 * H)
+            buf["adx"] = mk(B, S, H)
         # per-network activation slots (critics D=1)
         for name in ("q1s", "q2s", "t1", "t2", "q1b", "q2b"):
             buf[name] = {"outs": mk(B, S, 1), "hS": mk(B, H), "cS": mk(B, H),
@@ -274,9 +312,17 @@ class FusedSacContinuousStep(GraphableStep):
         else:
             e.seq_lstm_wgrad_multi(x, hx0, self.wgB_tab, 2, 1, **kw)
 
-    def _actor_fwd(self, x, hx0, cx0):
+    def _actor_fwd(self, x, hx0, cx0, out="moA"):
         e = ext()
         c = self.actor_core
+        if self.tile_rows:
+            buf = self.buf
+            e.seq_lstm_fwd_tile(
+                x, hx0, cx0, c.body_w, c.body_b, c.w_ih, c.w_hh, c.b_g,
+                c.heads_w, c.heads_b, buf[out], buf["hA"], buf["cA"],
+                buf["stA"],
+            )
+            return buf[out], buf["stA"]
         mo, _, _, stash = e.seq_lstm_forward(
             x, hx0, cx0, c.body_w, c.body_b, c.w_ih, c.w_hh, c.b_g,
             c.heads_w, c.heads_b,
@@ -286,10 +332,15 @@ class FusedSacContinuousStep(GraphableStep):
     def _actor_bwd_wgrad(self, gouts, stash, x, hx0, cx0, norm):
         e = ext()
         core = self.actor_core
-        _, _, _, dgates, dxb = e.seq_lstm_backward_core(
-            gouts, None, None, stash, x, cx0, core.body_w, core.w_ih,
-            core.w_hh, core.heads_w,
-        )
+        if self.tile_rows:
+            dgates, dxb = self.buf["adg"], self.buf["adx"]
+            e.seq_lstm_bwd_tile(gouts, stash, cx0, core.w_ih, core.w_hh,
+                                core.heads_w, dgates, dxb)
+        else:
+            _, _, _, dgates, dxb = e.seq_lstm_backward_core(
+                gouts, None, None, stash, x, cx0, core.body_w, core.w_ih,
+                core.w_hh, core.heads_w,
+            )
         gs = [core.body_w.grad, core.body_b.grad, core.w_ih.grad,
               core.w_hh.grad, core.b_g.grad, core.heads_w.grad,
               core.heads_b.grad]
@@ -438,14 +489,19 @@ class FusedSacContinuousStep(GraphableStep):
         fir = batch["is_fir"].reshape(B, S)
         log_alpha = u.log_alpha.data.view(1)
         single = self.grad_reducer is None
+        tile = self.tile_rows
+        fwd_multi = (e.seq_lstm_fwd_tile_multi if tile
+                     else e.seq_lstm_forward_multi)
+        bwd_multi = (e.seq_lstm_bwd_tile_multi if tile
+                     else e.seq_lstm_backward_multi)
 
         # 1. actor fwd + reparameterized sample
         moA, stA = self._actor_fwd(x, hx0, cx0)
         e.sacc_sample(moA, self.rng, buf["eps1"], buf["a1"], buf["logpi1"])
 
         # 2. twin critics on the fresh sample — ONE dual-body launch
-        e.seq_lstm_forward_multi(x, hx0, cx0, self.fwdS_cores, self.fwdS_outs,
-                                 2, 1, F2=A, half=half)
+        fwd_multi(x, hx0, cx0, self.fwdS_cores, self.fwdS_outs, 2, 1, F2=A,
+                  half=half)
         qp1 = buf["q1s"]["outs"]
         qp2 = buf["q2s"]["outs"]
 
@@ -453,11 +509,11 @@ class FusedSacContinuousStep(GraphableStep):
         e.sacc_min_mask(qp1, qp2, buf["gq1p"], buf["gq2p"], buf["dact"])
 
         # 4. cross-network dminQ/da — ONE multi launch, atomic accumulate
-        e.seq_lstm_backward_multi(x, cx0, self.bwdP_in, self.bwdP_out, 2, 1,
-                                  F2=A, half=half, accum_dx2=True)
+        bwd_multi(x, cx0, self.bwdP_in, self.bwdP_out, 2, 1, F2=A, half=half,
+                  accum_dx2=True)
 
         # 5. analytic actor + temperature gradients (+ Adam clock prep)
-        dmoA = torch.empty_like(moA)
+        dmoA = buf["dmoA"] if tile else torch.empty_like(moA)
         clk = u.actor_optimizer if self.adam_aa is not None else None
         e.sacc_actor_grad(
             moA, buf["eps1"], buf["a1"], buf["dact"], qp1.reshape(-1),
@@ -481,7 +537,7 @@ class FusedSacContinuousStep(GraphableStep):
             u.alpha_optimizer._update()  # no clip: norm unused
 
         # 7. post-update sample
-        moA2, _ = self._actor_fwd(x, hx0, cx0)
+        moA2, _ = self._actor_fwd(x, hx0, cx0, out="moA2")
         e.sacc_sample(moA2, self.rng, buf["eps2"], buf["a2"], buf["logpi2"])
 
         # 8. target critics on a2 + behavior critics on the batch actions —
@@ -489,8 +545,8 @@ class FusedSacContinuousStep(GraphableStep):
         #    batch actions are copied into the persistent actb buffer the
         #    table references, so non-graph callers stay correct)
         buf["actb"].copy_(batch["act"].reshape(B, S, A), non_blocking=True)
-        e.seq_lstm_forward_multi(x, hx0, cx0, self.fwdT_cores, self.fwdT_outs,
-                                 4, 1, F2=A, half=half)
+        fwd_multi(x, hx0, cx0, self.fwdT_cores, self.fwdT_outs, 4, 1, F2=A,
+                  half=half)
 
         # 9. critic losses (head grads land in the persistent gq buffers)
         e.sacc_critic_loss(
@@ -504,8 +560,7 @@ class FusedSacContinuousStep(GraphableStep):
         )
         # 10. twin-critic backward + MFMA wgrads (encoder grads ride the
         #     same launch as dual-body segments)
-        e.seq_lstm_backward_multi(x, cx0, self.bwdB_in, self.bwdB_out, 2, 1,
-                                  F2=A, half=half)
+        bwd_multi(x, cx0, self.bwdB_in, self.bwdB_out, 2, 1, F2=A, half=half)
         self._critic_wgrad(x, hx0)
         self._opt(u.critic_optimizer)
 
