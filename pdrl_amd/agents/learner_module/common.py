@@ -74,13 +74,16 @@ class BaseUpdater:
                 f"vmpo_mid_kernel must be 'block' or 'wide', got "
                 f"{vmpo_mid_kernel!r}")
         rows_kernel = getattr(self.params, "rows_kernel", "row")
-        if rows_kernel not in ("row", "tile"):
+        tile_hidden = {"tile": 64, "tile128": 128}
+        if rows_kernel != "row" and rows_kernel not in tile_hidden:
             raise ValueError(
-                f"rows_kernel must be 'row' or 'tile', got {rows_kernel!r}")
-        if rows_kernel == "tile" and int(self.params.hidden_size) != 64:
+                "rows_kernel must be 'row', 'tile' or 'tile128', got "
+                f"{rows_kernel!r}")
+        if (rows_kernel in tile_hidden
+                and int(self.params.hidden_size) != tile_hidden[rows_kernel]):
             raise ValueError(
-                "rows_kernel 'tile' is built for hidden_size 64, got "
-                f"{self.params.hidden_size}")
+                f"rows_kernel {rows_kernel!r} is built for hidden_size "
+                f"{tile_hidden[rows_kernel]}, got {self.params.hidden_size}")
         if not (self.device.type == "cuda" and ops.available()):
             return None
         if not getattr(optimizer, "is_fused", False):

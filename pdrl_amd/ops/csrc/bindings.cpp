@@ -58,6 +58,16 @@ void seq_lstm_bwd_tile_hip(const at::Tensor&, const at::Tensor&,
                            const at::Tensor&, const at::Tensor&,
                            const at::Tensor&, const at::Tensor&, at::Tensor&,
                            at::Tensor&);
+void seq_lstm_fwd_tile128_hip(
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, const at::Tensor&, const at::Tensor&,
+    const at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&, at::Tensor&,
+    at::Tensor&);
+void seq_lstm_bwd_tile128_hip(const at::Tensor&, const at::Tensor&,
+                              const at::Tensor&, const at::Tensor&,
+                              const at::Tensor&, const at::Tensor&,
+                              at::Tensor&, at::Tensor&);
 void seq_lstm_fwd_tile_multi_hip(const at::Tensor&, const at::Tensor&,
                                  const at::Tensor&, const at::Tensor&,
                                  const at::Tensor&, long, long, long, long);
@@ -497,6 +507,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("seq_lstm_bwd_tile", &seq_lstm_bwd_tile_hip,
         "BPTT for 16 batch rows per workgroup on MFMA (H=64): dgates and dxb "
         "of leaf inputs, from the stash of either forward",
+        py::arg("gouts"), py::arg("stash"), py::arg("c0"), py::arg("w_ih"),
+        py::arg("w_hh"), py::arg("heads_w"), py::arg("dgates"),
+        py::arg("dxb"));
+  m.def("seq_lstm_fwd_tile128", &seq_lstm_fwd_tile128_hip,
+        "forward for 16 batch rows per workgroup on MFMA (H=128), any "
+        "S >= 1: xb·w_ih + b_g of every step first, parked in xw_scratch "
+        "(B,S,4H), then the recurrence with w_hh resident; same tensors as "
+        "the row forward, all outputs caller-allocated",
+        py::arg("x"), py::arg("h0"), py::arg("c0"), py::arg("body_w"),
+        py::arg("body_b"), py::arg("w_ih"), py::arg("w_hh"), py::arg("b_g"),
+        py::arg("heads_w"), py::arg("heads_b"), py::arg("outs"),
+        py::arg("hS"), py::arg("cS"), py::arg("stash"),
+        py::arg("xw_scratch"));
+  m.def("seq_lstm_bwd_tile128", &seq_lstm_bwd_tile128_hip,
+        "BPTT for 16 batch rows per workgroup on MFMA (H=128): dgates in the "
+        "time loop, dxb in a second phase, from the stash of either forward",
         py::arg("gouts"), py::arg("stash"), py::arg("c0"), py::arg("w_ih"),
         py::arg("w_hh"), py::arg("heads_w"), py::arg("dgates"),
         py::arg("dxb"));

@@ -46,6 +46,16 @@ swapped for csrc/seq_lstm_tile.hip, 16 batch rows per workgroup on MFMA —
   (V-MPO: vmpo_mid | vmpo_mid_wide → vmpo_grad_rows) → seq_lstm_bwd_tile
 — on the workspace's buffers, then the weight-grad and optimizer launches.
 
+Row tiles at H=128 (rows_kernel="tile128", hidden size 128 only, any
+algorithm, any S >= 1 — the row forward stops at S = 32;
+profiles/rows_tile128.md): the same sequence with csrc/seq_lstm_tile128.hip,
+16 batch rows per workgroup of 8 waves. Only one of w_ih / w_hh fits the
+registers, so seq_lstm_fwd_tile128 first computes xb·w_ih + b_g of every step
+into a (B, S, 4H) scratch tensor — the workspace's dgates buffer, idle until
+the backward — and keeps w_hh resident over the time loop;
+seq_lstm_bwd_tile128 runs dh = dgates·w_hhᵀ in the time loop and
+dxb = relu'(xb)·(dgates·w_ihᵀ) in a second phase.
+
 No host syncs anywhere; stats are read back only at the log interval.
 With hipGraph capture (`use_graph`), the whole step replays as one graph
 launch — single-rank; multi-rank splits into two graphs around the
@@ -74,7 +84,9 @@ _ALGO_ID = {"IMPALA": 0, "PPO": 1, "PPO-C": 2, "V-MPO": 3}  # csrc/loss_row.h
 _WGRAD_MAX_ROWS = 8192          # row-pointer table of the sweep wgrad (LDS)
 WGRAD_KERNELS = ("sweep", "split")
 VMPO_MID_KERNELS = ("block", "wide")
-ROWS_KERNELS = ("row", "tile")
+ROWS_KERNELS = ("row", "tile")   # shared with the SAC steps
+ONPOLICY_ROWS_KERNELS = ROWS_KERNELS + ("tile128",)
+_TILE_HIDDEN = {"tile": 64, "tile128": 128}  # the width each tile is built for
 _ROW_STEP_MAX_LDS_BYTES = 64 * 1024  # dynamic LDS of one launch
 _VMPO_MID_LDS_BYTES = 56 * 1024  # vmpo_mid keeps s_adv + s_psi (BT each) in LDS
 
@@ -159,12 +171,14 @@ class FusedOnPolicyStep(GraphableStep):
         if vmpo_mid_kernel not in VMPO_MID_KERNELS:
             raise ValueError(f"vmpo_mid_kernel must be 'block' or 'wide', got "
                              f"{vmpo_mid_kernel!r}")
-        if rows_kernel not in ROWS_KERNELS:
-            raise ValueError(f"rows_kernel must be 'row' or 'tile', got "
-                             f"{rows_kernel!r}")
-        if rows_kernel == "tile" and core.w_ih.size(0) != 64:
-            raise ValueError("rows_kernel 'tile' is built for hidden size 64, "
-                             f"got {core.w_ih.size(0)}")
+        if rows_kernel not in ONPOLICY_ROWS_KERNELS:
+            raise ValueError(f"rows_kernel must be 'row', 'tile' or 'tile128', "
+                             f"got {rows_kernel!r}")
+        if (rows_kernel in _TILE_HIDDEN
+                and core.w_ih.size(0) != _TILE_HIDDEN[rows_kernel]):
+            raise ValueError(f"rows_kernel {rows_kernel!r} is built for hidden "
+                             f"size {_TILE_HIDDEN[rows_kernel]}, got "
+                             f"{core.w_ih.size(0)}")
         self.wgrad_kernel = wgrad_kernel
         self.vmpo_mid_kernel = vmpo_mid_kernel
         self.rows_kernel = rows_kernel
@@ -188,7 +202,7 @@ class FusedOnPolicyStep(GraphableStep):
         self.fused_rows = core.w_ih.size(0) == 64 and bool(
             int(os.environ.get("PDRL_FWDLOSS", "1")))
         # the row tiles take the separate launches, on workspace buffers
-        self.tile_rows = rows_kernel == "tile"
+        self.tile_rows = rows_kernel in _TILE_HIDDEN
         if self.tile_rows:
             self.fused_rows = False
         # forward + loss + BPTT in one launch wherever nothing crosses rows
@@ -350,8 +364,14 @@ class FusedOnPolicyStep(GraphableStep):
                                 ws["cS"], stash, *loss_args, **pre)
         elif self.tile_rows:
             outs, stash = ws["outs"], ws["stash"]
-            e.seq_lstm_fwd_tile(x, hx0, cx0, *weights, outs, ws["hS"],
-                                ws["cS"], stash)
+            if self.rows_kernel == "tile128":
+                # dgates is idle until the backward: the forward parks its
+                # input projections there
+                e.seq_lstm_fwd_tile128(x, hx0, cx0, *weights, outs, ws["hS"],
+                                       ws["cS"], stash, ws["dgates"])
+            else:
+                e.seq_lstm_fwd_tile(x, hx0, cx0, *weights, outs, ws["hS"],
+                                    ws["cS"], stash)
             e.onpolicy_loss_rows(outs, *loss_args, **pre)
         else:
             outs, _, _, stash = e.seq_lstm_forward(x, hx0, cx0, *weights)
@@ -394,8 +414,11 @@ class FusedOnPolicyStep(GraphableStep):
                                      *coefs)
             if self.tile_rows:
                 dgates, dxb = ws["dgates"], ws["dxb"]
-                e.seq_lstm_bwd_tile(gouts, stash, cx0, c.w_ih, c.w_hh,
-                                    c.heads_w, dgates, dxb)
+                bwd_tile = (e.seq_lstm_bwd_tile128
+                            if self.rows_kernel == "tile128"
+                            else e.seq_lstm_bwd_tile)
+                bwd_tile(gouts, stash, cx0, c.w_ih, c.w_hh, c.heads_w,
+                         dgates, dxb)
                 return hx0, stash, dgates, dxb, {}
             _, _, _, dgates, dxb = e.seq_lstm_backward_core(
                 gouts, None, None, stash, x, cx0, *bwd_weights)
