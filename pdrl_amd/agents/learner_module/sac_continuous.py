@@ -72,9 +72,10 @@ class SACContinuousUpdater(BaseUpdater):
         if rows_kernel not in ("row", "tile"):
             raise ValueError(
                 f"rows_kernel must be 'row' or 'tile', got {rows_kernel!r}")
-        if rows_kernel == "tile" and int(self.params.hidden_size) != 64:
+        if (rows_kernel == "tile"
+                and int(self.params.hidden_size) not in (64, 128)):
             raise ValueError(
-                "rows_kernel 'tile' is built for hidden_size 64, got "
+                "rows_kernel 'tile' is built for hidden_size 64 or 128, got "
                 f"{self.params.hidden_size}")
         if not (self.device.type == "cuda" and ops.available()):
             return None

@@ -74,6 +74,13 @@ void seq_lstm_fwd_tile_multi_hip(const at::Tensor&, const at::Tensor&,
 void seq_lstm_bwd_tile_multi_hip(const at::Tensor&, const at::Tensor&,
                                  const at::Tensor&, const at::Tensor&, long,
                                  long, long, long, bool);
+void seq_lstm_fwd_tile128_multi_hip(const at::Tensor&, const at::Tensor&,
+                                    const at::Tensor&, const at::Tensor&,
+                                    const at::Tensor&, const at::Tensor&, long,
+                                    long, long, long);
+void seq_lstm_bwd_tile128_multi_hip(const at::Tensor&, const at::Tensor&,
+                                    const at::Tensor&, const at::Tensor&, long,
+                                    long, long, long, bool);
 long seq_lstm_row_step_lds_bytes(long, long, long);
 long seq_lstm_row_step_split_lds_bytes(long, long, long);
 bool seq_lstm_row_step_uses_split(long, long, long);
@@ -535,6 +542,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("seq_lstm_bwd_tile_multi", &seq_lstm_bwd_tile_multi_hip,
         "seq_lstm_backward_multi on row tiles (H=64): dgates/dxb [+ dx2] of "
         "leaf inputs, the same device pointer tables",
+        py::arg("x"), py::arg("c0"), py::arg("in_tab"), py::arg("out_tab"),
+        py::arg("C"), py::arg("D"), py::arg("F2") = 0, py::arg("half") = 0,
+        py::arg("accum_dx2") = false);
+  m.def("seq_lstm_fwd_tile128_multi", &seq_lstm_fwd_tile128_multi_hip,
+        "seq_lstm_forward_multi on row tiles at H=128: xb·w_ih + b_g of "
+        "every step first, parked in the (B,S,4H) scratch tensors behind "
+        "xw_tab [C], then the recurrence with w_hh resident; any S >= 1, the "
+        "same device pointer tables",
+        py::arg("x"), py::arg("h0"), py::arg("c0"), py::arg("core_tab"),
+        py::arg("out_tab"), py::arg("xw_tab"), py::arg("C"), py::arg("D"),
+        py::arg("F2") = 0, py::arg("half") = 0);
+  m.def("seq_lstm_bwd_tile128_multi", &seq_lstm_bwd_tile128_multi_hip,
+        "seq_lstm_backward_multi on row tiles at H=128: dgates in the time "
+        "loop, dxb [+ dx2] of leaf inputs in a second phase; the same device "
+        "pointer tables, every dgates slot set",
         py::arg("x"), py::arg("c0"), py::arg("in_tab"), py::arg("out_tab"),
         py::arg("C"), py::arg("D"), py::arg("F2") = 0, py::arg("half") = 0,
         py::arg("accum_dx2") = false);

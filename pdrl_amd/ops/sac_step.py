@@ -42,17 +42,25 @@ rows; the split kernels size nothing by B*S, so with "split" there is no row
 cap. The 8192-row gate of SeqLSTMCore.forward (the autograd path) is not
 touched.
 
-rows_kernel="tile" (the parameter file's "rows_kernel"; H = 64, meant for
-B in the thousands: profiles/sac_tile.md) runs the legacy sequence, single-
-or multi-rank, with its recurrent launches on row tiles, 16 batch rows per
-workgroup on MFMA, and nothing else changed:
-  seq_lstm_forward_multi  -> seq_lstm_fwd_tile_multi   (step 1)
-  seq_lstm_backward_multi -> seq_lstm_bwd_tile_multi   (step 8)
-  seq_lstm_forward        -> seq_lstm_fwd_tile         (step 5)
-  seq_lstm_backward_core  -> seq_lstm_bwd_tile         (step 3)
-(csrc/seq_lstm_tile_multi.hip takes the pointer tables built here as they
-are; csrc/seq_lstm_tile.hip writes into buffers this step owns.) The
-8-launch DAG fuses loss phases into the row kernels and is not taken.
+rows_kernel="tile" (the parameter file's "rows_kernel"; H = 64 or 128,
+meant for B in the thousands: profiles/sac_tile.md, profiles/sac_tile128.md)
+runs the legacy sequence, single- or multi-rank, with its recurrent launches
+on row tiles, 16 batch rows per workgroup on MFMA, and nothing else changed.
+The kernel pair follows the model width (one width for all five networks):
+  step  "row"                    H = 64                   H = 128
+  1     seq_lstm_forward_multi   seq_lstm_fwd_tile_multi  ..fwd_tile128_multi
+  8     seq_lstm_backward_multi  seq_lstm_bwd_tile_multi  ..bwd_tile128_multi
+  5     seq_lstm_forward         seq_lstm_fwd_tile        ..fwd_tile128
+  3     seq_lstm_backward_core   seq_lstm_bwd_tile        ..bwd_tile128
+(csrc/seq_lstm_tile_multi.hip and csrc/seq_lstm_tile128_multi.hip take the
+pointer tables built here as they are; the single-network kernels write into
+buffers this step owns.) The H = 128 forwards park xb·w_ih + b_g of every
+step in a (B, S, 4H) scratch tensor per network: a network that has a dgates
+buffer lends it, idle until its backward; the two targets get buffers of
+their own, allocated with the workspace. The table of scratch pointers is
+built once with the other tables. The 8-launch DAG fuses loss phases into the
+row kernels and is not taken. Any other width raises ValueError, and so does
+the on-policy step's value "tile128".
 """
 from __future__ import annotations
 
@@ -60,6 +68,8 @@ import torch
 
 from . import ext
 from .fused_step import ROWS_KERNELS, WGRAD_KERNELS, GraphableStep
+
+TILE_HIDDEN = (64, 128)  # the widths rows_kernel="tile" has kernels for
 
 _SAC_STATS = ["loss-actor", "loss-alpha", "alpha", "entropy", "loss-value"]
 
@@ -74,12 +84,13 @@ class FusedSacStep(GraphableStep):
             raise ValueError(f"rows_kernel must be 'row' or 'tile', got "
                              f"{rows_kernel!r}")
         hidden = updater.actor.core.w_ih.size(0)
-        if rows_kernel == "tile" and hidden != 64:
-            raise ValueError("rows_kernel 'tile' is built for hidden size 64, "
-                             f"got {hidden}")
+        if rows_kernel == "tile" and hidden not in TILE_HIDDEN:
+            raise ValueError("rows_kernel 'tile' is built for hidden size 64 "
+                             f"or 128, got {hidden}")
         self.wgrad_kernel = wgrad_kernel
         self.rows_kernel = rows_kernel
         self.tile_rows = rows_kernel == "tile"
+        self.tile128 = self.tile_rows and hidden == 128
         self.u = updater
         self.params = updater.params
         self.grad_reducer = updater.grad_reducer
@@ -193,6 +204,11 @@ class FusedSacStep(GraphableStep):
             a["dgates"] = mk(B, S, 4 * H)
             a["dxb"] = mk(B, S, H)
             buf["mo2"] = mk(B, S, D)
+        if self.tile128:
+            # scratch of the H = 128 forwards: a dgates buffer is idle until
+            # its network's backward and is lent; the targets have none
+            for name in ("t1", "t2"):
+                buf[name]["xw"] = mk(B, S, 4 * H)
         self.buf = buf
 
         def t64(rows):
@@ -220,6 +236,10 @@ class FusedSacStep(GraphableStep):
         self.fwd1_outs = t64([orow(buf["actor"]), orow(buf["q1"]),
                               orow(buf["q2"]), orow(buf["t1"]),
                               orow(buf["t2"])])
+        if self.tile128:
+            self.fwd1_xw = t64([buf[n].get("xw", buf[n].get("dgates"))
+                                .data_ptr() for n in
+                                ("actor", "q1", "q2", "t1", "t2")])
 
         def birow(name):
             core, b = c[name], buf[name]
@@ -285,8 +305,9 @@ class FusedSacStep(GraphableStep):
         e = ext()
         if self.tile_rows:
             dgates, dxb = self.buf["actor"]["dgates"], self.buf["actor"]["dxb"]
-            e.seq_lstm_bwd_tile(gouts, stash, cx0, core.w_ih, core.w_hh,
-                                core.heads_w, dgates, dxb)
+            (e.seq_lstm_bwd_tile128 if self.tile128 else e.seq_lstm_bwd_tile)(
+                gouts, stash, cx0, core.w_ih, core.w_hh, core.heads_w, dgates,
+                dxb)
         else:
             _, _, _, dgates, dxb = e.seq_lstm_backward_core(
                 gouts, None, None, stash, x, cx0, core.body_w, core.w_ih,
@@ -420,8 +441,12 @@ class FusedSacStep(GraphableStep):
         #    launch (the targets' params are constant until the Polyak
         #    update at step 9, so their forward commutes with steps 2-5)
         tile = self.tile_rows
-        (e.seq_lstm_fwd_tile_multi if tile else e.seq_lstm_forward_multi)(
-            x, hx0, cx0, self.fwd1_cores, self.fwd1_outs, 5, D)
+        if self.tile128:
+            e.seq_lstm_fwd_tile128_multi(x, hx0, cx0, self.fwd1_cores,
+                                         self.fwd1_outs, self.fwd1_xw, 5, D)
+        else:
+            (e.seq_lstm_fwd_tile_multi if tile else e.seq_lstm_forward_multi)(
+                x, hx0, cx0, self.fwd1_cores, self.fwd1_outs, 5, D)
         moA1 = buf["actor"]["outs"]
         mq1, mq2 = buf["q1"]["outs"], buf["q2"]["outs"]
 
@@ -454,9 +479,12 @@ class FusedSacStep(GraphableStep):
         ac = self.cores["actor"]
         if tile:
             ab, moA2 = buf["actor"], buf["mo2"]
-            e.seq_lstm_fwd_tile(
+            # at H = 128 the actor's dgates, dead behind its weight
+            # gradients, is the scratch again
+            (e.seq_lstm_fwd_tile128 if self.tile128 else e.seq_lstm_fwd_tile)(
                 x, hx0, cx0, ac.body_w, ac.body_b, ac.w_ih, ac.w_hh, ac.b_g,
                 ac.heads_w, ac.heads_b, moA2, ab["hS"], ab["cS"], ab["stash"],
+                *((ab["dgates"],) if self.tile128 else ()),
             )
         else:
             moA2, _, _, _ = e.seq_lstm_forward(
@@ -474,7 +502,9 @@ class FusedSacStep(GraphableStep):
             p.gamma, p.reward_scale,
         )
         # 8. twin-critic backward + MFMA weight grads — one launch each
-        (e.seq_lstm_bwd_tile_multi if tile else e.seq_lstm_backward_multi)(
+        (e.seq_lstm_bwd_tile128_multi if self.tile128
+         else e.seq_lstm_bwd_tile_multi if tile
+         else e.seq_lstm_backward_multi)(
             x, cx0, self.bwd_in, self.bwd_out, 2, D)
         self._critic_wgrad(x, hx0)
         self._opt(u.critic_optimizer)

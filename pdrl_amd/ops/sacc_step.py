@@ -43,19 +43,29 @@ seq_lstm_wgrad_split_out. With "split" fits() has no row cap (the sweep
 kernels' B*S-entry LDS row table is the only reason for the 8192 rows). The
 8192-row gate of SeqLSTMCore.forward (the autograd path) is not touched.
 
-rows_kernel="tile" (the parameter file's "rows_kernel"; H = 64, meant for
-B in the thousands: profiles/sac_tile.md) runs the legacy sequence, single-
-or multi-rank, with its recurrent launches on row tiles, 16 batch rows per
-workgroup on MFMA, and nothing else changed:
-  seq_lstm_forward_multi  -> seq_lstm_fwd_tile_multi   (steps 2 and 8,
-                             dual body: x2 per network from the table)
-  seq_lstm_backward_multi -> seq_lstm_bwd_tile_multi   (step 4, with dx2
-                             accumulated into dact, and step 10)
-  seq_lstm_forward        -> seq_lstm_fwd_tile         (steps 1 and 7)
-  seq_lstm_backward_core  -> seq_lstm_bwd_tile         (step 6)
-(csrc/seq_lstm_tile_multi.hip takes the pointer tables built here as they
-are; csrc/seq_lstm_tile.hip writes into buffers this step owns.) The
-11-launch DAG fuses loss phases into the row kernels and is not taken.
+rows_kernel="tile" (the parameter file's "rows_kernel"; H = 64 or 128,
+meant for B in the thousands: profiles/sac_tile.md, profiles/sac_tile128.md)
+runs the legacy sequence, single- or multi-rank, with its recurrent launches
+on row tiles, 16 batch rows per workgroup on MFMA, and nothing else changed.
+The kernel pair follows the model width (one width for all networks):
+  "row"                    H = 64                   H = 128
+  seq_lstm_forward_multi   seq_lstm_fwd_tile_multi  ..fwd_tile128_multi
+      (steps 2 and 8, dual body: x2 per network from the table)
+  seq_lstm_backward_multi  seq_lstm_bwd_tile_multi  ..bwd_tile128_multi
+      (step 4, with dx2 accumulated into dact, and step 10)
+  seq_lstm_forward         seq_lstm_fwd_tile        ..fwd_tile128
+      (steps 1 and 7)
+  seq_lstm_backward_core   seq_lstm_bwd_tile        ..bwd_tile128
+      (step 6)
+(csrc/seq_lstm_tile_multi.hip and csrc/seq_lstm_tile128_multi.hip take the
+pointer tables built here as they are; the single-network kernels write into
+buffers this step owns.) The H = 128 forwards park xb·w_ih + b_g of every
+step in a (B, S, 4H) scratch tensor per network: a network that has a dgates
+buffer lends it, idle until its backward; the two targets get buffers of
+their own, allocated with the workspace. The tables of scratch pointers are
+built once with the other tables. The 11-launch DAG fuses loss phases into
+the row kernels and is not taken. Any other width raises ValueError, and so
+does the on-policy step's value "tile128".
 """
 from __future__ import annotations
 
@@ -63,6 +73,7 @@ import torch
 
 from . import ext
 from .fused_step import ROWS_KERNELS, WGRAD_KERNELS, GraphableStep
+from .sac_step import TILE_HIDDEN
 
 _SACC_STATS = ["loss-actor", "loss-alpha", "alpha", "entropy", "loss-value"]
 
@@ -77,12 +88,13 @@ class FusedSacContinuousStep(GraphableStep):
             raise ValueError(f"rows_kernel must be 'row' or 'tile', got "
                              f"{rows_kernel!r}")
         hidden = updater.actor.core.w_ih.size(0)
-        if rows_kernel == "tile" and hidden != 64:
-            raise ValueError("rows_kernel 'tile' is built for hidden size 64, "
-                             f"got {hidden}")
+        if rows_kernel == "tile" and hidden not in TILE_HIDDEN:
+            raise ValueError("rows_kernel 'tile' is built for hidden size 64 "
+                             f"or 128, got {hidden}")
         self.wgrad_kernel = wgrad_kernel
         self.rows_kernel = rows_kernel
         self.tile_rows = rows_kernel == "tile"
+        self.tile128 = self.tile_rows and hidden == 128
         self.u = updater
         self.params = updater.params
         self.grad_reducer = updater.grad_reducer
@@ -211,6 +223,11 @@ class FusedSacContinuousStep(GraphableStep):
             buf[name]["dxb"] = mk(B, S, H)
         for name in ("q1b", "q2b"):
             buf[name]["gq"] = mk(B, S, 1)
+        if self.tile128:
+            # scratch of the H = 128 forwards: a dgates buffer is idle until
+            # its network's backward and is lent; the targets have none
+            for name in ("t1", "t2"):
+                buf[name]["xw"] = mk(B, S, 4 * H)
         self.buf = buf
 
         def t64(rows):
@@ -239,6 +256,13 @@ class FusedSacContinuousStep(GraphableStep):
         ])
         self.fwdT_outs = t64([orow(buf["t1"]), orow(buf["t2"]),
                               orow(buf["q1b"]), orow(buf["q2b"])])
+        if self.tile128:
+            def xws(*names):
+                return t64([buf[n].get("xw", buf[n].get("dgates")).data_ptr()
+                            for n in names])
+
+            self.fwdS_xw = xws("q1s", "q2s")
+            self.fwdT_xw = xws("t1", "t2", "q1b", "q2b")
 
         def birow(core, gq, b, want_dgates=True):
             return [gq.data_ptr(), b["stash"].data_ptr(),
@@ -317,10 +341,12 @@ class FusedSacContinuousStep(GraphableStep):
         c = self.actor_core
         if self.tile_rows:
             buf = self.buf
-            e.seq_lstm_fwd_tile(
+            # at H = 128 the actor's dgates, idle in both forwards, is the
+            # scratch
+            (e.seq_lstm_fwd_tile128 if self.tile128 else e.seq_lstm_fwd_tile)(
                 x, hx0, cx0, c.body_w, c.body_b, c.w_ih, c.w_hh, c.b_g,
                 c.heads_w, c.heads_b, buf[out], buf["hA"], buf["cA"],
-                buf["stA"],
+                buf["stA"], *((buf["adg"],) if self.tile128 else ()),
             )
             return buf[out], buf["stA"]
         mo, _, _, stash = e.seq_lstm_forward(
@@ -334,8 +360,9 @@ class FusedSacContinuousStep(GraphableStep):
         core = self.actor_core
         if self.tile_rows:
             dgates, dxb = self.buf["adg"], self.buf["adx"]
-            e.seq_lstm_bwd_tile(gouts, stash, cx0, core.w_ih, core.w_hh,
-                                core.heads_w, dgates, dxb)
+            (e.seq_lstm_bwd_tile128 if self.tile128 else e.seq_lstm_bwd_tile)(
+                gouts, stash, cx0, core.w_ih, core.w_hh, core.heads_w, dgates,
+                dxb)
         else:
             _, _, _, dgates, dxb = e.seq_lstm_backward_core(
                 gouts, None, None, stash, x, cx0, core.body_w, core.w_ih,
@@ -490,18 +517,23 @@ class FusedSacContinuousStep(GraphableStep):
         log_alpha = u.log_alpha.data.view(1)
         single = self.grad_reducer is None
         tile = self.tile_rows
-        fwd_multi = (e.seq_lstm_fwd_tile_multi if tile
+        fwd_multi = (e.seq_lstm_fwd_tile128_multi if self.tile128
+                     else e.seq_lstm_fwd_tile_multi if tile
                      else e.seq_lstm_forward_multi)
-        bwd_multi = (e.seq_lstm_bwd_tile_multi if tile
+        bwd_multi = (e.seq_lstm_bwd_tile128_multi if self.tile128
+                     else e.seq_lstm_bwd_tile_multi if tile
                      else e.seq_lstm_backward_multi)
+        # the H = 128 forward takes its scratch table behind out_tab
+        xwS = (self.fwdS_xw,) if self.tile128 else ()
+        xwT = (self.fwdT_xw,) if self.tile128 else ()
 
         # 1. actor fwd + reparameterized sample
         moA, stA = self._actor_fwd(x, hx0, cx0)
         e.sacc_sample(moA, self.rng, buf["eps1"], buf["a1"], buf["logpi1"])
 
         # 2. twin critics on the fresh sample — ONE dual-body launch
-        fwd_multi(x, hx0, cx0, self.fwdS_cores, self.fwdS_outs, 2, 1, F2=A,
-                  half=half)
+        fwd_multi(x, hx0, cx0, self.fwdS_cores, self.fwdS_outs, *xwS, 2, 1,
+                  F2=A, half=half)
         qp1 = buf["q1s"]["outs"]
         qp2 = buf["q2s"]["outs"]
 
@@ -545,8 +577,8 @@ class FusedSacContinuousStep(GraphableStep):
         #    batch actions are copied into the persistent actb buffer the
         #    table references, so non-graph callers stay correct)
         buf["actb"].copy_(batch["act"].reshape(B, S, A), non_blocking=True)
-        fwd_multi(x, hx0, cx0, self.fwdT_cores, self.fwdT_outs, 4, 1, F2=A,
-                  half=half)
+        fwd_multi(x, hx0, cx0, self.fwdT_cores, self.fwdT_outs, *xwT, 4, 1,
+                  F2=A, half=half)
 
         # 9. critic losses (head grads land in the persistent gq buffers)
         e.sacc_critic_loss(

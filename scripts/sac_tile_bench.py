@@ -4,11 +4,14 @@
     python scripts/sac_tile_bench.py [--repeats 5] [--iters 200]
                                      [--algos SAC SAC-Continuous]
                                      [--batches 128 512 1536 2048 4096]
+                                     [--hidden 64]
 
 ``updater.step`` (one graph replay of the fused DAG) for SAC and
 SAC-Continuous at S=5, H=64 and ``"wgrad_kernel": "split"``, so every batch
 size stays on the HIP DAG: ``"row"`` (the 8- and 11-launch DAGs) against
-``"tile"`` (the legacy launch sequence on row tiles).
+``"tile"`` (the legacy launch sequence on row tiles). ``--hidden 128`` times
+the H=128 kernels (csrc/seq_lstm_tile128_multi.hip); there ``"row"`` is the
+legacy sequence too, the 8- and 11-launch DAGs being built for H=64.
 
 Every shape is warmed up, the two settings alternate block by block inside
 one process, a block is ``--iters`` calls between two device events, and each
@@ -63,7 +66,7 @@ def report(name: str, values: list[float], **cfg):
     }), flush=True)
 
 
-def make_step(algo: str, B: int, rows_kernel: str):
+def make_step(algo: str, B: int, rows_kernel: str, hidden: int = 64):
     """``updater.step`` on one synthetic batch with either recurrent kernel."""
     from bench import env_shape, make_synthetic_batch
     from pdrl_amd.agents.learner_module import switch_module
@@ -73,6 +76,7 @@ def make_step(algo: str, B: int, rows_kernel: str):
     p.algo, p.batch_size, p.seq_len = algo, B, 5
     p.obs_dim, p.n_actions, _ = env_shape(algo)
     p.wgrad_kernel, p.rows_kernel = "split", rows_kernel
+    p.hidden_size = hidden
     upd_cls, model_cls = switch_module(algo)
     torch.manual_seed(0)
     model = model_cls(p.obs_dim, p.n_actions, p.seq_len, p.hidden_size)
@@ -89,6 +93,7 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--algos", nargs="+", default=list(ALGOS), choices=ALGOS)
     ap.add_argument("--batches", nargs="+", type=int, default=list(BATCHES))
+    ap.add_argument("--hidden", type=int, default=64, choices=(64, 128))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark needs the GPU"
     from pdrl_amd import ops
@@ -97,10 +102,10 @@ def main():
     assert args.repeats >= 5, "a range needs at least five blocks"
     for algo in args.algos:
         for B in args.batches:
-            fns = {k: make_step(algo, B, k) for k in KERNELS}
+            fns = {k: make_step(algo, B, k, args.hidden) for k in KERNELS}
             for k, v in alternate(fns, args.iters, args.repeats).items():
                 report("sac_step", v, algo=algo, rows_kernel=k,
-                       wgrad_kernel="split", B=B, S=5)
+                       wgrad_kernel="split", B=B, S=5, H=args.hidden)
 
 
 if __name__ == "__main__":

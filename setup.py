@@ -23,6 +23,7 @@ SRC = [
     "pdrl_amd/ops/csrc/seq_lstm_tile.hip",
     "pdrl_amd/ops/csrc/seq_lstm_tile_multi.hip",
     "pdrl_amd/ops/csrc/seq_lstm_tile128.hip",
+    "pdrl_amd/ops/csrc/seq_lstm_tile128_multi.hip",
     "pdrl_amd/ops/csrc/wgrad.hip",
     "pdrl_amd/ops/csrc/wgrad_split.hip",
     "pdrl_amd/ops/csrc/wgrad_split_multi.hip",
